@@ -10,8 +10,19 @@ Each step runs both query passes over all queries (evidence -> domain index,
 factor-row gather/product, global max, normalised write).  The factor tables
 are plan constants (fitted CPDs x target x observed columns x N, independent
 of evidence values) built once per plan; ``--rebuild-tables`` re-runs that
-build every step, and the default run also reports that figure as
-``value_rebuild_tables``.  N > 1 (``--gpus N`` starts N ranks itself through a
+build every step, and a ``--full`` run also reports that figure as
+``value_rebuild_tables``.
+
+A plain run sets up, warms up, times ``--steps`` steps and prints the line
+(``value``, ``ms_per_step``, ``timing`` of the timed region itself).  What
+takes runs of its own -- the CPU baseline, the roofline with its back-to-back
+launches, ``value_rebuild_tables``, the other reassembly choice at N > 1 --
+is measured only under ``--full``.  ``--dump-outputs DIR`` writes what the
+last timed step returned (``pdf.npy``: the normalised [Q, N] rows;
+``domain.npy``: the target domain, both float32) after the timed region;
+every input is seeded, so the same arguments give the same inputs.
+
+N > 1 (``--gpus N`` starts N ranks itself through a
 child ``torch.distributed.run`` unless it already runs under one): the batch
 grows with N (weak scaling), each rank owns 65 536 queries and the ranks
 exchange the global max with one RCCL all-reduce of the block max words
@@ -21,18 +32,19 @@ overlaps the next step's launch (distributed.ShardedStepper;
 step at N=1 over a one-rank RCCL communicator).  At N > 1 ``value`` is
 north_star's step: the shard's raw launch, the all-reduce + scale AND the RCCL
 all-gather that reassembles the full [Q, N] marginal tensor on every rank
-(``value_kind`` "gathered"); the step that leaves the tensor sharded is timed
-after it as ``value_rank_local`` (``--rank-local`` swaps the two).  The line
+(``value_kind`` "gathered"); under ``--full`` the step that leaves the tensor
+sharded is timed after it as ``value_rank_local`` (``--rank-local`` swaps the
+two).  The line
 carries DESIGN.md's ``projection`` for both at that N.  A rank that makes no
 host progress for ``--watchdog`` seconds prints its step / ring state / last
 collective and exits non-zero (distributed.Watchdog).
 
 ``timing`` itemises ms_per_step: host enqueue time per step, the GPU-side
-event region, the same launches back-to-back with the queue held full (a
-kernel duration independent of the host), and what lies outside the region
-(first submit, final sync wake-up).
+event region, what lies outside the region (first submit, final sync
+wake-up) and, under ``--full``, the same launches back-to-back with the queue
+held full (a kernel duration independent of the host).
 
-Prints ONE JSON line (rank 0).  Extra fields: ``roofline`` for the dominant
+Prints ONE JSON line (rank 0).  Extra fields under ``--full``: ``roofline`` for the dominant
 kernel -- the single-launch fused query kernel at N=1 (the write pass when the
 two-launch path runs) -- timed with HIP events recorded by the library on the
 launch stream inside the timed region; ``roofline.traffic`` = its per-launch
@@ -136,6 +148,13 @@ def parse(argv=None):
     ap.add_argument("--rebuild-tables", action="store_true",
                     help="re-run k_build_tables in every step (the factor tables are plan constants; by default "
                          "they are built once per plan, as in serving)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline figure: the CPU baseline, the roofline of the "
+                         "dominant kernel with its back-to-back launches, the rebuild-tables figure and, at N>1, the "
+                         "other reassembly choice (a plain run sets up, warms up, times --steps steps and prints)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (pdf rows and target "
+                         "domain) as DIR/<name>.npy (float32; a seeded row sample beyond 64 MB in all)")
     return ap.parse_args(argv)
 
 
@@ -338,6 +357,31 @@ def backlogged_launch_us(step, K: int, stream) -> float:
     return ev[2].elapsed_time(ev[3]) / K * 1e3
 
 
+DUMP_BUDGET_BYTES = 64 * 2 ** 20  # --dump-outputs: all files together
+
+
+def dump_outputs(path: str, arrays: dict) -> dict:
+    """Write each array of ``arrays`` (name -> tensor, as the caller of the
+    timed step received it) to ``path``/<name>.npy in float32.  An array whose
+    equal share of the 64 MB budget is too small is cut to a fixed, seeded
+    sample of its rows (the sorted row indices, as float64 like every file
+    here is floating point, in <name>_rows.npy).  Returns what was written,
+    for the result line."""
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // 64 * 63 // max(1, len(arrays))  # 1/64 kept for the .npy headers
+    written = {}
+    for name, t in arrays.items():
+        rows = None
+        row_bytes = 4 * max(1, t.numel() // max(1, t.shape[0])) + 8  # a float32 row + its float64 index
+        if t.shape[0] * row_bytes > share:
+            rows = np.sort(np.random.default_rng(20).choice(t.shape[0], share // row_bytes, replace=False))
+            t = t[torch.as_tensor(rows, device=t.device)]
+            np.save(os.path.join(path, name + "_rows.npy"), rows.astype(np.float64))
+        np.save(os.path.join(path, name + ".npy"), t.detach().to("cpu", torch.float32).contiguous().numpy())
+        written[name] = {"shape": list(t.shape), "sampled_rows": rows is not None}
+    return written
+
+
 def main():
     a = parse()
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -353,7 +397,7 @@ def main():
     names = [c for c in cols if c != target]
     ev_np = sample_evidence(data, cols, names, Q, seed=1000 + rank)
     cpu = None
-    if rank == 0 and not sharded and not a.no_cpu_baseline:
+    if a.full and rank == 0 and not sharded and not a.no_cpu_baseline:
         # first, while no process has touched the GPU: its worker pool forks
         cpu = cpu_baseline(data, cols, edges, ev_np, target, d, a.cpu_seconds)
     wd = None
@@ -455,16 +499,21 @@ def main():
     torch.cuda.synchronize()
     # the library launches on torch's current stream: these events bracket
     # every launch (instrumentation, recorded before the host clock starts)
+    per_step_events = a.full and not sharded and not fused
+    last = K - 1 if a.dump_outputs else -1
+    result = None
     ev0.record()
     t0 = time.perf_counter()
-    per_step_events = not sharded and not fused
     for i in range(K):
-        # two-launch path: HIP events recorded inside the library around the
-        # passes of every 8th step (the sharded step and the fused launch are
+        # --full, two-launch path: HIP events recorded inside the library around
+        # the passes of every 8th step (the sharded step and the fused launch are
         # timed over the region: per-step event records cost ~3 us per step)
         if per_step_events:
             bn.engine.timed = i % 8 == 7
-        step()
+        if i == last:
+            result = step()  # --dump-outputs: what the last timed step hands its caller
+        else:
+            step()
     t_enq = time.perf_counter()  # host done enqueueing the K steps
     stepper.wait()
     ev1.record()
@@ -496,10 +545,17 @@ def main():
             ht = c.host_timing()
             timing["stepper_host_us"] = {"gather_alloc": round(ht[0], 2), "launch_and_exchange": round(ht[1], 2)}
 
+    dumped = None
+    if result is not None and rank == 0:
+        # the last timed step's return value: rank 0's normalised rows (the whole
+        # [Q, N] tensor when the step gathers it) and the target's domain
+        dumped = dump_outputs(a.dump_outputs, {"pdf": result[0], "domain": result[1]})
+    result = None
+
     roofline = None
     ntimed, tmax_ms, twrite_ms = bn.engine.timing() if not sharded else (0, 0.0, 0.0)
     bn.engine.check_status()
-    if fused:
+    if fused and a.full:
         # one launch per step: average launch duration = HIP-event time of the timed region / K
         ntimed, twrite_ms = K, region_us / K * 1e-3
         # the same launches with the queue kept full (no host gaps): a kernel duration
@@ -543,7 +599,7 @@ def main():
             roofline["frac_backlogged"] = round(bytes_q / kb / 1e9 / HBM_PEAK_GBS, 4)
         if not fused:
             roofline["first_launch_us"], roofline["second_launch_us"] = round(tmax * 1e6, 2), round(twrite * 1e6, 2)
-    if sharded and gather and world > 1:
+    if a.full and sharded and gather and world > 1:
         # with the reassembly, each rank receives the other ranks' rows every
         # step over xGMI: (world - 1) x Q x 4N bytes -- the dominant transfer
         t_step = region_us / K * 1e-6
@@ -558,7 +614,7 @@ def main():
                         avg_us=round(t_step * 1e6, 2), algorithmic_bytes_per_launch=bytes_in, timed_steps=K,
                         timing="HIP events on rank 0's launch stream around the timed region / K steps; bytes = "
                                "rows received from the other ranks per step")
-    elif sharded:
+    elif a.full and sharded:
         # rank-local sharded step: ONE raw launch per step on the launch stream
         # (folded: it also divides an earlier step's rows by that step's
         # all-reduced max, cbn_plan_run_fold; else k_scale_batch per group on
@@ -583,7 +639,7 @@ def main():
 
     rccl_ranks = stepper.comm_ranks() if sharded else None  # before close(): the headline step's communicator
     other = None
-    if modes["other_kind"] is not None:
+    if a.full and modes["other_kind"] is not None:
         # the same step with the other reassembly choice: each rank keeping its
         # rows (value_rank_local) or, with --rank-local, the all-gather of the
         # full [Q, N] tensor on every rank (value_gathered)
@@ -598,7 +654,7 @@ def main():
         other = Q * world * K / timed_steps(K)
 
     cold = None
-    if not sharded and not a.rebuild_tables:
+    if a.full and not sharded and not a.rebuild_tables:
         bn.engine.cache_tables = False
         for _ in range(5):
             step()
@@ -629,8 +685,10 @@ def main():
             "value_kind": modes["value_kind"],
             "roofline": roofline, "cpu_baseline": cpu, "timing": timing,
             "tables": "rebuilt every step" if a.rebuild_tables else "built once per plan",
-            "evidence_batches": len(batches),
+            "evidence_batches": len(batches), "full": a.full,
         }
+        if dumped is not None:
+            line["dumped_outputs"] = dumped
         line.update(multi_gpu_fields(a.gpus, world, rccl_ranks))
         if cold is not None:
             line["value_rebuild_tables"] = round(cold, 1)

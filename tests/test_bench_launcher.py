@@ -74,6 +74,38 @@ def test_n_gt_1_value_is_the_gathered_step():
         bench.multi_gpu_fields(2, 2, 1)
 
 
+def test_plain_run_options():
+    """--full and --dump-outputs are off by default; --steps is the number of
+    timed steps as given."""
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert not a.full and a.dump_outputs is None and a.steps == 7 and a.warmup == 2
+    a = bench.parse(["--full", "--dump-outputs", "d"])
+    assert a.full and a.dump_outputs == "d"
+
+
+def test_dump_outputs_writes_float32_within_budget(tmp_path, monkeypatch):
+    """Small arrays are written whole; beyond the byte budget a fixed, seeded
+    row sample is written with its row indices, the same on every call."""
+    import numpy as np
+    import torch
+
+    pdf = torch.arange(40 * 8, dtype=torch.float32).reshape(40, 8)
+    dom = torch.arange(8, dtype=torch.float64).unsqueeze(0).expand(40, -1)
+    w = bench.dump_outputs(str(tmp_path / "a"), {"pdf": pdf, "domain": dom})
+    got = np.load(tmp_path / "a" / "pdf.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, pdf.numpy())
+    assert np.load(tmp_path / "a" / "domain.npy").dtype == np.float32
+    assert w == {"pdf": {"shape": [40, 8], "sampled_rows": False}, "domain": {"shape": [40, 8], "sampled_rows": False}}
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 1024)
+    for d in ("b", "c"):
+        w = bench.dump_outputs(str(tmp_path / d), {"pdf": pdf, "domain": dom})
+        assert w["pdf"]["sampled_rows"] and w["pdf"]["shape"][0] < 40
+    rows = np.load(tmp_path / "b" / "pdf_rows.npy")
+    assert np.array_equal(rows, np.load(tmp_path / "c" / "pdf_rows.npy")) and np.all(np.diff(rows) > 0)
+    assert np.array_equal(np.load(tmp_path / "b" / "pdf.npy"), pdf.numpy()[rows.astype(int)])
+    assert sum(p.stat().st_size for p in (tmp_path / "b").iterdir()) <= 1024 + 4 * 128  # + the four .npy headers
+
+
 STANDIN_MODES = """
 import json, os, sys
 sys.path.insert(0, {root!r})

@@ -1,6 +1,6 @@
 """Itemise the driver's bench command from its rocprofv3 kernel trace
 (round 4): the k_query_staged<2> dispatches of bench.py
---steps K --warmup W in order -- W warmup launches, then the K timed ones,
+--steps K --warmup W --full in order -- W warmup launches, then the K timed ones,
 then bench's back-to-back calibration launches -- with each dispatch's
 duration and the GPU idle gap before it, plus the bench line's own timing
 fields.  Usage: python tools/driver_timeline.py TRACE_DIR BENCH_JSON_LINE_FILE OUT.json"""
@@ -28,7 +28,7 @@ def main():
     back = list(range(W + K + 4, len(rows)))  # bench.backlogged_launch_us: 4 host-timed, then the queued ones
     back = [i for i in back if i < W + K + 4 + max(K, 100)]
     avg = lambda xs: round(sum(xs) / len(xs), 3) if xs else None
-    res = dict(command="rocprofv3 --kernel-trace --stats -- python3 bench.py --gpus 1 --steps %d --warmup %d" % (K, W),
+    res = dict(command="rocprofv3 --kernel-trace --stats -- python3 bench.py --gpus 1 --steps %d --warmup %d --full" % (K, W),
                dispatches=len(rows),
                timed=dict(duration_us=[round(dur[i], 2) for i in timed], gap_before_us=[round(gap[i], 2) for i in timed],
                           avg_duration_us=avg([dur[i] for i in timed]),

@@ -9,14 +9,14 @@
 #   pytest        the GPU suite (PYTEST_K / PYTEST_FILES narrow it; PYTEST_X= runs past failures)
 #   smoke         __graft_entry__.smoke()
 #   driverN       the driver's bench command (--gpus 1 --steps 20 --warmup 5), N times
-#   bench         python bench.py (default: 200 steps, the CPU baseline)
-#   sharded       bench.py --sharded --no-cpu-baseline (the N>1 step over a one-rank communicator)
+#   bench         python bench.py --full (default: 200 steps; --full adds the CPU baseline, roofline, ...)
+#   sharded       bench.py --sharded --full --no-cpu-baseline (the N>1 step over a one-rank communicator)
 #   alarm|cont|grid|chain16|direct   tools/bench_<name>.py (configs[2] / [3] / [4], N = 16 chain,
 #                 direct plans; BENCH_ARGS passes arguments)
-#   prof          rocprofv3 --kernel-trace --stats of the driver's command
-#   fetch|write   one rocprofv3 --pmc FETCH_SIZE (WRITE_SIZE) pass of bench.py --steps 40 (HBM traffic)
+#   prof          rocprofv3 --kernel-trace --stats of the driver's command with --full
+#   fetch|write   one rocprofv3 --pmc FETCH_SIZE (WRITE_SIZE) pass of bench.py --full --steps 40 (HBM traffic)
 #   summary       tools/profile_summary.py over prof / fetch / write -> profiles/$TAG_*
-#   pmcNAME       one rocprofv3 --pmc pass of the driver's command with the counters in $PMC_NAME
+#   pmcNAME       one rocprofv3 --pmc pass of the driver's command (--full) with the counters in $PMC_NAME
 #   profcfg       rocprofv3 --kernel-trace --stats of tools/bench_{alarm,cont,grid}.py ($CONFIGS)
 #   pmcgrid       the configs[4] kernel's SQ / TCC / TCP counters, four passes, tools/pmc_table.py
 #   pmcparam      the parametric query kernel's SQ counters (tools/prof_param.py $PROF_ARGS)
@@ -63,26 +63,26 @@ for step in "$@"; do
         line $O/driver_$i.json "driver $i"
       done ;;
     bench)
-      timeout -k 10 300 python3 bench.py > $O/bench_default.json 2> $O/bench_default.err || exit $?
+      timeout -k 10 300 python3 bench.py --full > $O/bench_default.json 2> $O/bench_default.err || exit $?
       line $O/bench_default.json default ;;
     sharded)
-      timeout -k 10 300 python3 bench.py --sharded --no-cpu-baseline > $O/bench_sharded.json 2> $O/bench_sharded.err || exit $?
+      timeout -k 10 300 python3 bench.py --sharded --full --no-cpu-baseline > $O/bench_sharded.json 2> $O/bench_sharded.err || exit $?
       line $O/bench_sharded.json sharded ;;
     alarm|cont|grid|chain16|direct)
       timeout -k 10 600 python3 tools/bench_$step.py ${BENCH_ARGS:-} > $O/$step.log 2>&1 || exit $?
       grep '^{' $O/$step.log | cut -c1-400 ;;
     prof)
       timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/prof -o run --output-format csv -- python3 bench.py --gpus 1 \
-        --steps 20 --warmup 5 > $O/prof_bench.json 2> $O/prof_bench.err || exit $?
+        --steps 20 --warmup 5 --full > $O/prof_bench.json 2> $O/prof_bench.err || exit $?
       rm -f $O/prof/run_kernel_trace.csv
       kstats $O/prof/run_kernel_stats.csv ;;
     fetch|write)
       c=FETCH_SIZE; [ $step = write ] && c=WRITE_SIZE
       timeout -s KILL 120 rocprofv3 --pmc $c --kernel-trace -d $O/pmc_$step -o run --output-format csv -- python3 bench.py \
-        --steps 40 --warmup 4 --no-cpu-baseline > $O/pmc_$step.json 2> $O/pmc_$step.err || exit $? ;;
+        --steps 40 --warmup 4 --full --no-cpu-baseline > $O/pmc_$step.json 2> $O/pmc_$step.err || exit $? ;;
     summary)
       timeout -k 10 120 python3 tools/profile_summary.py --tag "${TAG:-r06}" --prof $O/prof --fetch $O/pmc_fetch \
-        --write $O/pmc_write --warmup 5 --steps 20 --command "rocprofv3 --kernel-trace --stats -- python3 bench.py --gpus 1 --steps 20 --warmup 5 (PMC: separate --pmc FETCH_SIZE / WRITE_SIZE passes, --steps 40)" \
+        --write $O/pmc_write --warmup 5 --steps 20 --command "rocprofv3 --kernel-trace --stats -- python3 bench.py --gpus 1 --steps 20 --warmup 5 --full (PMC: separate --pmc FETCH_SIZE / WRITE_SIZE passes, --steps 40)" \
         > $O/summary.log 2>&1 || exit $?
       cp profiles/${TAG:-r06}_summary.json profiles/${TAG:-r06}_kernel_stats.csv $O/  # (gpurun copies gpurun_out back)
       tail -5 $O/summary.log ;;
@@ -116,7 +116,7 @@ for step in "$@"; do
         *)
           var=PMC_$name; counters=${!var}
           timeout -s KILL 120 rocprofv3 --pmc $counters -d $O/pmc_$name -o run -- python3 bench.py --gpus 1 --steps 20 \
-            --warmup 5 --no-cpu-baseline > $O/pmc_$name.json 2> $O/pmc_$name.err || exit $?
+            --warmup 5 --full --no-cpu-baseline > $O/pmc_$name.json 2> $O/pmc_$name.err || exit $?
           find $O/pmc_$name -name "*counter_collection.csv" | head -2 ;;
       esac ;;
     profcfg)
