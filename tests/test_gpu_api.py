@@ -2,8 +2,9 @@
 the default ``device="cuda"`` (no index), stale plans after a refit, the
 timeout reporting of the single-launch path, caller-supplied ``out``
 validation, and the pipelined sharded stepper with the all-gather reassembly
-(one rank over RCCL).  Tolerance where values are compared: rtol 1e-5, atol
-1e-7 (north star)."""
+(one rank over RCCL).  Tolerance where values are compared: tests/parity.py
+(rtol 1e-5 on every entry plus the subnormal-rounding floor over the oracle's
+unnormalised batch max)."""
 import ctypes
 import random
 
@@ -14,9 +15,9 @@ import torch
 from continuousbayesiannetwork_amd import BayesianNetwork, _native
 from helpers import chain_data, make_bn, sample_evidence
 from oracle.ref_infer import OracleBN
+from parity import FLT_MIN, SUB, assert_golden_close, assert_marginals_close, n_factors, oracle_reference
 
 pytestmark = pytest.mark.gpu
-RTOL, ATOL = 1e-5, 1e-7
 
 
 def _t(ev, dev):
@@ -34,8 +35,8 @@ def test_default_cuda_device_without_index(gpu):
     ev = _t(sample_evidence(data, cols, names, 777, 2), "cuda")
     a, _ = bn.infer("X7", ev, N_max=8)
     b, _ = bn.infer("X7", ev, N_max=8)
-    ref, _ = OracleBN(edges, cols, data).infer("X7", {k: v.cpu().numpy() for k, v in ev.items()}, 8)
-    np.testing.assert_allclose(a.cpu().numpy(), ref, rtol=RTOL, atol=ATOL)
+    ref, _, kw = oracle_reference(OracleBN(edges, cols, data), "X7", {k: v.cpu().numpy() for k, v in ev.items()}, 8)
+    assert_marginals_close(a.cpu().numpy(), ref, **kw)
     np.testing.assert_array_equal(a.cpu().numpy(), b.cpu().numpy())
     rows, _, words, scale = bn.engine.infer_raw("X7", ev, 8)
     scale(rows, words)
@@ -67,8 +68,8 @@ def test_refit_drops_cached_plans(gpu):
     node = OracleNode("X5", ["X4"])
     node.fit(y, x)
     ora.nodes["X5"] = node
-    ref, _ = ora.infer("X5", ev, 4)
-    np.testing.assert_allclose(got.cpu().numpy(), ref, rtol=RTOL, atol=ATOL)
+    ref, _, kw = oracle_reference(ora, "X5", ev, 4)
+    assert_marginals_close(got.cpu().numpy(), ref, **kw)
 
 
 def test_timeout_is_reported_on_next_call(gpu):
@@ -193,7 +194,7 @@ def test_variable_elimination_query_matches_reference_golden(gpu):
         pdf, dom = (ve.query(m["target"], ev, N_max=m["N_max"]) if hasattr(ve, "query")
                     else ve.infer(m["target"], ev, None, N_max=m["N_max"]))
         np.testing.assert_array_equal(dom.cpu().numpy(), g["domain"])
-        np.testing.assert_allclose(pdf.cpu().numpy(), g["pdf"], rtol=RTOL, atol=ATOL)
+        assert_golden_close(pdf.cpu().numpy(), "chain5_d4_q1024_parent")
 
 
 def test_native_runner_path_matches_and_falls_back(gpu):
@@ -215,8 +216,8 @@ def test_native_runner_path_matches_and_falls_back(gpu):
     b, db = bn.infer("X7", dict(ev), N_max=8)  # runner path (a new dict, same keys)
     np.testing.assert_array_equal(a.cpu().numpy(), b.cpu().numpy())
     assert torch.equal(da, db) and db.shape == (777, 8)
-    ref, _ = OracleBN(edges, cols, data).infer("X7", {k: v.cpu().numpy() for k, v in ev.items()}, 8)
-    np.testing.assert_allclose(b.cpu().numpy(), ref, rtol=RTOL, atol=ATOL)
+    ref, _, kw = oracle_reference(OracleBN(edges, cols, data), "X7", {k: v.cpu().numpy() for k, v in ev.items()}, 8)
+    assert_marginals_close(b.cpu().numpy(), ref, **kw)
     # another key order: the general path (its own fast path), same values
     rev = {k: ev[k] for k in reversed(list(ev))}
     c, _ = bn.infer("X7", rev, N_max=8)
@@ -227,7 +228,7 @@ def test_native_runner_path_matches_and_falls_back(gpu):
     np.testing.assert_array_equal(bn.infer("X7", ev64, N_max=8)[0].cpu().numpy(), a.cpu().numpy())
     evc = dict(ev)
     evc["X3"] = ev["X3"].cpu()
-    np.testing.assert_allclose(bn.infer("X7", evc, N_max=8)[0].cpu().numpy(), ref, rtol=RTOL, atol=ATOL)
+    assert_marginals_close(bn.infer("X7", evc, N_max=8)[0].cpu().numpy(), ref, **kw)
     # the reference's errors still raise
     with pytest.raises(AttributeError):
         bn.infer("X7", None, N_max=8)
@@ -260,8 +261,8 @@ def test_native_runner_path_matches_and_falls_back(gpu):
     node = OracleNode("X7", ["X6"])
     node.fit(y, x)
     ora.nodes["X7"] = node
-    ref2, _ = ora.infer("X7", {k: v.cpu().numpy() for k, v in ev.items()}, 8)
-    np.testing.assert_allclose(got.cpu().numpy(), ref2, rtol=RTOL, atol=ATOL)
+    ref2, _, kw2 = oracle_reference(ora, "X7", {k: v.cpu().numpy() for k, v in ev.items()}, 8)
+    assert_marginals_close(got.cpu().numpy(), ref2, **kw2)
     got2, _ = bn.infer("X7", dict(ev), N_max=8)  # the rebuilt plan's runner
     np.testing.assert_array_equal(got2.cpu().numpy(), got.cpu().numpy())
 
@@ -309,8 +310,8 @@ def test_evidence_width_raises_like_the_reference(gpu):
     assert not strided["X6"].is_contiguous() and strided["X6"].shape == (777, 1)
     s1, _ = bn.infer("X7", strided, N_max=8)
     np.testing.assert_array_equal(s1.cpu().numpy(), a.cpu().numpy())
-    ref, _ = OracleBN(edges, cols, data).infer("X7", {k: v.cpu().numpy() for k, v in ev.items()}, 8)
-    np.testing.assert_allclose(s1.cpu().numpy(), ref, rtol=RTOL, atol=ATOL)
+    ref, _, kw = oracle_reference(OracleBN(edges, cols, data), "X7", {k: v.cpu().numpy() for k, v in ev.items()}, 8)
+    assert_marginals_close(s1.cpu().numpy(), ref, **kw)
     # the raw launch and the sharded paths
     with pytest.raises(RuntimeError, match=msg):
         eng.infer_raw("X7", wide, 8)
@@ -345,28 +346,50 @@ def test_global_table_plan_with_many_factors_and_few_slots_takes_a_fast_kernel(g
     buffers, so the plan is not dropped to the generic k_query kernel.  A
     100-node chain d = 32 whose nodes X12, X22, X32 also have X10, X20, X30
     as parents (three 1 024-row tables: a 400 KB image, beyond LDS), evidence
-    on 7 nodes; the marginals match the oracle."""
+    on 7 nodes.
+
+    The data keeps the 100-factor products inside fp32's normal range (a free
+    factor's column j is mean_k P(v_j | v_k), about the node's marginal at
+    v_j, so every node's marginal sits on two levels, 0.485 each; every level
+    still occurs in every column, so the tables keep their shapes): each of
+    the 31 compared rows has two entries >= FLT_MIN on the oracle's side (a
+    condition on the inputs, asserted), the batch max is ~1.2e-34.  The
+    engine's UNnormalised rows match the oracle's at rtol 1e-5 plus 100
+    subnormal steps, and the normalised marginals match through the helper,
+    all finite."""
     rng = np.random.default_rng(17)
     S, d, n = 20000, 32, 100
+    pm = np.full(d, 0.03 / 30)
+    pm[0] = pm[1] = 0.485
     X = np.zeros((S, n), np.int64)
-    X[:, 0] = rng.integers(0, d, S)
+    X[:, 0] = rng.choice(d, S, p=pm)
     for i in range(1, n):
-        X[:, i] = (X[:, i - 1] + (rng.random(S) < 0.3) * rng.integers(0, d, S)) % d
-        if i in (12, 22, 32):
-            X[:, i] = (X[:, i - 1] + X[:, i - 2]) % d
+        src = (X[:, i - 1] + X[:, i - 2]) % d if i in (12, 22, 32) else X[:, i - 1]
+        draw = rng.choice(d, S, p=pm)
+        X[:, i] = np.where(rng.random(S) < 0.04, src, draw)
+    assert all(len(np.unique(X[:, i])) == d for i in range(n))
     data = X.astype(np.float32)
     cols = [f"X{i}" for i in range(n)]
     edges = [(cols[i - 1], cols[i]) for i in range(1, n)] + [(cols[i - 2], cols[i]) for i in (12, 22, 32)]
     names = ["X10", "X11", "X20", "X21", "X30", "X31", "X98"]  # (X98: the target needs an observed parent)
     ev = sample_evidence(data, cols, names, 3000, 4)
     bn = make_bn(BayesianNetwork, edges, cols, data, device=gpu)
-    pdf, _ = bn.infer("X99", {k: torch.tensor(v, device=gpu) for k, v in ev.items()}, N_max=32)
+    evt = {k: torch.tensor(v, device=gpu) for k, v in ev.items()}
+    pdf, _ = bn.infer("X99", evt, N_max=32)
     fp = bn.engine._fast[("X99", tuple(ev.keys()), 32)]
     flags = _native.load().cbn_plan_flags(fp.plan.handle)
     assert flags & (_native.CBN_PLAN_FAST | _native.CBN_PLAN_SLOTS), flags
     assert not flags & _native.CBN_PLAN_LDS  # a global-table plan
     sub = np.arange(0, 3000, 97)
     random.seed(0)
-    ref, _ = OracleBN(edges, cols, data).infer_raw("X99", {k: v[sub] for k, v in ev.items()}, 32)
-    p = pdf.cpu().numpy()[sub]
-    np.testing.assert_allclose(p / p.max(), ref / ref.max(), rtol=1e-5, atol=1e-7)
+    ora = OracleBN(edges, cols, data)
+    ref_raw, _ = ora.infer_raw("X99", {k: v[sub] for k, v in ev.items()}, 32)
+    assert (ref_raw >= FLT_MIN).sum(1).min() >= 2  # the inputs: normal values in every compared row
+    p = pdf.cpu().numpy()
+    assert np.isfinite(p).all() and p.max() == 1.0
+    raw = bn.engine.infer_raw("X99", evt, 32)[0].cpu().numpy()
+    np.testing.assert_allclose(raw[sub], ref_raw, rtol=1e-5, atol=100 * SUB)
+    # the 31 rows over their own max on both sides (the oracle cannot run all 3 000)
+    ps = p[sub]
+    assert_marginals_close(ps / ps.max(), ref_raw / ref_raw.max(), raw_max=float(ref_raw.max()),
+                           n_factors=n_factors(ora, "X99"))

@@ -78,6 +78,8 @@ def test_grid_coalesced_index_phase_equals_per_lane(gpu, tmp_path):
     ev = sample_evidence(data, cols, names, 200003, 3)
     rows = np.asarray(res["rows"])
     random.seed(0)
-    ref, _ = OracleBN(edges, cols, data).infer(target, {k: v[rows] for k, v in ev.items()}, 64)
+    from parity import assert_marginals_close, oracle_reference
+
+    ref, _, kw = oracle_reference(OracleBN(edges, cols, data), target, {k: v[rows] for k, v in ev.items()}, 64)
     got = np.load(outp)
-    np.testing.assert_allclose(got / got.max(), ref, rtol=1e-5, atol=1e-7)
+    assert_marginals_close(got / got.max(), ref, **kw)

@@ -1,11 +1,16 @@
 """HIP path vs the reference (golden vectors) and vs the CPU oracle.
 
-Tolerance (stated per the north star): rtol 1e-5, atol 1e-7 on fp32 pdfs --
-the HIP tables average the parent axes in a different order than torch.mean.
-Domains, shapes, zero patterns and error types must match exactly.
+Tolerance (tests/parity.py): rtol 1e-5 (the north star's fp32 bar) on every
+entry of the max-normalised marginals -- the HIP tables average the parent
+axes in a different order than torch.mean -- plus the subnormal-rounding
+floor n_factors * 2^-149 / (the ORACLE's unnormalised batch max), never above
+the former atol 1e-7.  Single factors (get_prob): rtol 1e-5 plus one
+subnormal step per summed term.  Domains, shapes, zero patterns and error
+types must match exactly.
 """
 import random
 
+import networkx as nx
 import numpy as np
 import pytest
 import torch
@@ -15,9 +20,11 @@ from continuousbayesiannetwork_amd.inference.engine import domain_index
 from golden_io import golden_error, golden_names, load_golden, width_n_only
 from helpers import alarm_like_data, chain_data, make_bn, random_dag_data, sample_evidence
 from oracle.ref_infer import OracleBN, OracleBruteForce, OracleNode
+from parity import (assert_factor_close, assert_golden_close, assert_marginals_close, engine_raw_rows, n_factors,
+                    oracle_raw, oracle_reference)
 
 pytestmark = pytest.mark.gpu
-RTOL, ATOL = 1e-5, 1e-7
+RTOL = 1e-5
 
 
 def _t(ev, dev):
@@ -42,7 +49,7 @@ def test_infer_matches_reference_golden(name, gpu):
     pdf, dom = bn.infer(m["target"], ev, N_max=m["N_max"])
     assert pdf.device.type == "cuda"
     np.testing.assert_array_equal(dom.cpu().numpy(), g["domain"])
-    np.testing.assert_allclose(pdf.cpu().numpy(), g["pdf"], rtol=RTOL, atol=ATOL)
+    assert_golden_close(pdf.cpu().numpy(), name, got_raw=engine_raw_rows(bn, name, ev))
     # a second call reuses the cached plan (or redraws, for oversampled domains)
     random.seed(m["seed"])
     pdf2, _ = bn.infer(m["target"], ev, N_max=m["N_max"])
@@ -71,11 +78,11 @@ def test_random_dags_match_oracle(case, gpu):
     if not any(p in ev for p in tpar):
         ev[tpar[0]] = sample_evidence(data, cols, [tpar[0]], Q, seed + 9)[tpar[0]]
     random.seed(seed)
-    ref, rdom = ora.infer(target, ev, N)
+    ref, rdom, kw = oracle_reference(ora, target, ev, N)
     random.seed(seed)
     pdf, dom = bn.infer(target, _t(ev, gpu), N_max=N)
     np.testing.assert_array_equal(dom.cpu().numpy(), rdom)
-    np.testing.assert_allclose(pdf.cpu().numpy(), ref, rtol=RTOL, atol=ATOL)
+    assert_marginals_close(pdf.cpu().numpy(), ref, **kw)
 
 
 def test_vec1_path_and_oversampled_domains(gpu):
@@ -86,11 +93,11 @@ def test_vec1_path_and_oversampled_domains(gpu):
     ev = sample_evidence(data, cols, ["X4", "X1"], 333, 5)
     for N, seed in [(5, 0), (7, 3), (3, 0)]:
         random.seed(seed)
-        ref, rdom = ora.infer("X5", ev, N)
+        ref, rdom, kw = oracle_reference(ora, "X5", ev, N)
         random.seed(seed)
         pdf, dom = bn.infer("X5", _t(ev, gpu), N_max=N)
         np.testing.assert_array_equal(dom.cpu().numpy(), rdom)
-        np.testing.assert_allclose(pdf.cpu().numpy(), ref, rtol=RTOL, atol=ATOL)
+        assert_marginals_close(pdf.cpu().numpy(), ref, **kw)
 
 
 def test_node_get_prob_matches_oracle(gpu):
@@ -110,7 +117,7 @@ def test_node_get_prob_matches_oracle(gpu):
             ref, rdom = on.get_prob(dict(q), N)
             pdf, dom, _ = nd.get_prob({k: torch.tensor(v, device=gpu) for k, v in q.items()}, N)
             assert tuple(pdf.shape) == ref.shape
-            np.testing.assert_allclose(pdf.cpu().numpy(), ref, rtol=RTOL, atol=ATOL)
+            assert_factor_close(pdf.cpu().numpy(), ref)  # each entry one joint / parent-marginal quotient
             np.testing.assert_array_equal(dom.cpu().numpy(), rdom)
 
 
@@ -129,16 +136,16 @@ def test_bruteforce_get_prob_matches_oracle(gpu):
     q = rng.integers(-1, 5, (300, 2, 1)).astype(np.float32)
     ref = ob.get_prob(pts, q)
     got = bf.get_prob(torch.tensor(pts, device=gpu), torch.tensor(q, device=gpu)).cpu().numpy()
-    np.testing.assert_allclose(got, ref, rtol=RTOL, atol=ATOL)
-    assert (got[ref == 0] == 0).all()
+    assert_factor_close(got, ref)
+    assert (got[ref == 0] == 0).all() and (ref > 0).sum() > 100
     # root / marginal form (query=None)
     ob0 = OracleBruteForce()
     ob0.fit(nd_, None)
     bf0 = BruteForce({"estimator_name": "brute_force"}, device=gpu)
     bf0.fit(torch.tensor(nd_, device=gpu), None)
     p0 = rng.integers(-1, 6, (1, 9)).astype(np.float32)
-    np.testing.assert_allclose(bf0.get_prob(torch.tensor(p0, device=gpu)).cpu().numpy(), ob0.get_prob(p0),
-                               rtol=RTOL, atol=ATOL)
+    # a marginal sums the node value's rows: at most 16 parent combinations each
+    assert_factor_close(bf0.get_prob(torch.tensor(p0, device=gpu)).cpu().numpy(), ob0.get_prob(p0), n_terms=16)
 
 
 def test_empty_and_single_query_edges(gpu):
@@ -148,9 +155,9 @@ def test_empty_and_single_query_edges(gpu):
         bn.infer("X3", {"X2": torch.zeros((0, 1), device=gpu)}, N_max=3)
     ora = OracleBN(edges, cols, data)
     ev = {"X2": np.array([[1.0]], np.float32)}
-    ref, _ = ora.infer("X3", ev, 3)
+    ref, _, kw = oracle_reference(ora, "X3", ev, 3)
     pdf, _ = bn.infer("X3", _t(ev, gpu), N_max=3)
-    np.testing.assert_allclose(pdf.cpu().numpy(), ref, rtol=RTOL, atol=ATOL)
+    assert_marginals_close(pdf.cpu().numpy(), ref, **kw)
 
 
 def _full_golden(name):
@@ -187,7 +194,10 @@ def test_full_batch_config1_matches_reference(gpu):
     assert rows.size == 65536 and p.shape == ref.shape
     np.testing.assert_array_equal(dom.cpu().numpy(), np.broadcast_to(rdom[:1], tuple(dom.shape)))
     assert float(p[m["argmax_row"]].max()) == 1.0 and float(p.max()) == 1.0
-    np.testing.assert_allclose(p, ref, rtol=RTOL, atol=ATOL)
+    # the batch max M of the unnormalised products: the oracle on the reference's argmax row alone
+    ora = OracleBN(edges, cols, data)
+    _, mx = oracle_raw(ora, "X19", {k: v[m["argmax_row"]:m["argmax_row"] + 1] for k, v in ev.items()}, 32)
+    assert_marginals_close(p, ref, raw_max=mx, n_factors=n_factors(ora, "X19"))
     # the raw launch + in-place scale (the sharded step's pieces) gives the same rows
     from continuousbayesiannetwork_amd.distributed import sharded_infer
 
@@ -210,7 +220,9 @@ def test_full_batch_config2_slice_matches_reference(gpu):
     p = pdf.cpu().numpy()
     np.testing.assert_array_equal(dom.cpu().numpy(), np.broadcast_to(rdom[:1], tuple(dom.shape)))
     assert float(p[m["argmax_row"]].max()) == 1.0 and float(p.max()) == 1.0
-    np.testing.assert_allclose(p[rows], ref, rtol=RTOL, atol=ATOL)
+    ora = OracleBN(edges, cols, data)
+    _, mx = oracle_raw(ora, "X35", {k: v[m["argmax_row"]:m["argmax_row"] + 1] for k, v in ev.items()}, 8)
+    assert_marginals_close(p[rows], ref, raw_max=mx, n_factors=n_factors(ora, "X35"))
 
 
 def test_full_size_config1_properties(gpu):
@@ -236,9 +248,9 @@ def test_full_size_config1_properties(gpu):
     rstar = int(np.argmax(p.max(1)))
     sub = np.append(np.arange(200, 200 + 257), rstar)
     ora = OracleBN(edges, cols, data)
-    ref, _ = ora.infer("X19", {k: v[sub] for k, v in ev.items()}, d)
+    ref, _, kw = oracle_reference(ora, "X19", {k: v[sub] for k, v in ev.items()}, d)
     assert ref[-1].max() == 1.0
-    np.testing.assert_allclose(p[sub], ref, rtol=RTOL, atol=ATOL)
+    assert_marginals_close(p[sub], ref, **kw)
 
 
 def test_split_passes_equal_fused_and_sharded(gpu):
@@ -288,11 +300,11 @@ def test_many_observed_parents_generic_and_global_paths(k, d, N, gpu):
     bn = make_bn(BayesianNetwork, edges, cols, data, device=gpu)
     ev = sample_evidence(data, cols, [f"P{i}" for i in range(k)], 700, 3, missing_frac=0.05)
     random.seed(1)
-    ref, rdom = ora.infer("C", ev, N)
+    ref, rdom, kw = oracle_reference(ora, "C", ev, N)
     random.seed(1)
     pdf, dom = bn.infer("C", _t(ev, gpu), N_max=N)
     np.testing.assert_array_equal(dom.cpu().numpy(), rdom)
-    np.testing.assert_allclose(pdf.cpu().numpy(), ref, rtol=RTOL, atol=ATOL)
+    assert_marginals_close(pdf.cpu().numpy(), ref, **kw)
 
 
 def test_more_factors_than_fast_path(gpu):
@@ -301,9 +313,9 @@ def test_more_factors_than_fast_path(gpu):
     ora = OracleBN(edges, cols, data)
     bn = make_bn(BayesianNetwork, edges, cols, data, device=gpu)
     ev = sample_evidence(data, cols, ["X38", "X20", "X3"], 900, 4)
-    ref, rdom = ora.infer("X39", ev, 3)
+    ref, rdom, kw = oracle_reference(ora, "X39", ev, 3)
     pdf, dom = bn.infer("X39", _t(ev, gpu), N_max=3)
-    np.testing.assert_allclose(pdf.cpu().numpy(), ref, rtol=RTOL, atol=ATOL)
+    assert_marginals_close(pdf.cpu().numpy(), ref, **kw)
 
 
 def test_table_cache_mode_matches(gpu):
@@ -339,8 +351,9 @@ def test_single_launch_matches_two_launch(Q, gpu):
     assert cap >= 65536
     np.testing.assert_array_equal(a.cpu().numpy(), b.cpu().numpy())
     if Q <= 64:
-        ref, _ = OracleBN(edges, cols, data).infer("X19", {k: v.cpu().numpy() for k, v in ev.items()}, 32)
-        np.testing.assert_allclose(b.cpu().numpy(), ref, rtol=RTOL, atol=ATOL)
+        ref, _, kw = oracle_reference(OracleBN(edges, cols, data), "X19", {k: v.cpu().numpy() for k, v in ev.items()},
+                                      32)
+        assert_marginals_close(b.cpu().numpy(), ref, **kw)
 
 
 @pytest.mark.parametrize("Q,shards", [(1001, 2), (65536, 8), (7, 3)])
@@ -460,11 +473,14 @@ def test_alarm_like_config2_matches_oracle(target, N, missing, gpu):
     ora = OracleBN(edges, cols, data)
     bn = make_bn(BayesianNetwork, edges, cols, data, device=gpu)
     random.seed(2)
-    ref, rdom = ora.infer(target, ev, N)
+    ref, rdom, kw = oracle_reference(ora, target, ev, N)
     random.seed(2)
     pdf, dom = bn.infer(target, _t(ev, gpu), N_max=N)
     np.testing.assert_array_equal(dom.cpu().numpy(), rdom)
-    np.testing.assert_allclose(pdf.cpu().numpy(), ref, rtol=RTOL, atol=ATOL)
+    # missing = 0.05 over the 36 evidence columns and N = 4 of the 8 levels: the
+    # oracle's rows are nonzero for 102 of the 384 queries (0.266), the rest are
+    # zero by construction (an off-domain value, brute_force.py:172-244)
+    assert_marginals_close(pdf.cpu().numpy(), ref, min_checked_rows=0.25 if missing == 0.05 else 0.5, **kw)
 
 
 def test_config2_cols_off_domain_rows_through_lds_and_global_tables(gpu):
@@ -499,8 +515,8 @@ def test_config2_cols_off_domain_rows_through_lds_and_global_tables(gpu):
     assert _native.load().cbn_plan_flags(fp.plan.handle) & _native.CBN_PLAN_COLS
     p = pdf.cpu().numpy()
     assert (p[:130] == 0).all() and p.max() == 1.0
-    ref, _ = OracleBN(edges, cols, data).infer("X35", ev, 8)
-    np.testing.assert_allclose(p, ref, rtol=RTOL, atol=ATOL)
+    ref, _, kw = oracle_reference(OracleBN(edges, cols, data), "X35", ev, 8)
+    assert_marginals_close(p, ref, **kw)  # 382 of the 512 rows are on the domain
 
 
 def test_alarm_like_config2_full_batch_properties(gpu):
@@ -521,29 +537,46 @@ def test_alarm_like_config2_full_batch_properties(gpu):
     np.testing.assert_array_equal(p[0], p[1])
     rstar = int(np.argmax(p.max(1)))
     sub = np.append(np.arange(0, Q, Q // 97)[:96], rstar)
-    ref, _ = OracleBN(edges, cols, data).infer("X35", {k: v[sub] for k, v in ev.items()}, 8)
+    ref, _, kw = oracle_reference(OracleBN(edges, cols, data), "X35", {k: v[sub] for k, v in ev.items()}, 8)
     assert ref[-1].max() == 1.0  # the GPU's argmax row is the oracle's too
-    np.testing.assert_allclose(p[sub], ref, rtol=RTOL, atol=ATOL)
+    assert_marginals_close(p[sub], ref, **kw)
 
 
 def test_grid_beyond_64_factors_and_evidence_columns(gpu):
     """configs[4] shape at a size the oracle handles: 9 x 9 grid DAG (81
     factors, 80 evidence columns -- beyond 64 of both), d = 4, vs the oracle
     (N = 4: one lane per query, the per-wave offset table of 81 factors does
-    not fit LDS, so this runs the generic kernel); sharded == single call."""
+    not fit LDS, so this runs the generic kernel); sharded == single call.
+
+    Data: every node's marginal sits on two of its four levels (0.485 each;
+    column j of the product is ~ prod_n P(n = v_j | its parents' evidence)), so
+    the 81-factor products stay in fp32's normal range (batch max ~2e-25).
+    With helpers.grid_data's near-uniform CPDs they were ~0.25^81: the batch
+    max was 2.8e-45, two subnormal steps, and the comparison checked 4 rows.
+    139 of the 300 queries carry no off-domain value (missing_frac 0.01 over
+    80 columns); those are the nonzero rows, all of them compared."""
     from continuousbayesiannetwork_amd.distributed import shard_evidence, sharded_infer
 
-    from helpers import grid_data
-
-    data, cols, edges = grid_data(30000, 2, side=9, d=4, keep=0.9)
+    rng = np.random.default_rng(2)
+    S, side, d = 30000, 9, 4
+    pm = np.array([0.485, 0.485, 0.015, 0.015])
+    X = np.zeros((S, side * side), np.int64)
+    edges = []
+    for i in range(side * side):
+        ps = ([i - 1] if i % side > 0 else []) + ([i - side] if i >= side else [])
+        edges += [(f"X{p}", f"X{i}") for p in ps]
+        draw = rng.choice(d, S, p=pm)
+        X[:, i] = np.where(rng.random(S) < 0.04, sum(X[:, p] for p in ps) // len(ps), draw) if ps else draw
+    assert all(len(np.unique(X[:, i])) == d for i in range(side * side))
+    data, cols = X.astype(np.float32), [f"X{i}" for i in range(side * side)]
     target, names = cols[-1], cols[:-1]
     ev = sample_evidence(data, cols, names, 300, 5, missing_frac=0.01)
     ora = OracleBN(edges, cols, data)
     bn = make_bn(BayesianNetwork, edges, cols, data, device=gpu)
-    ref, rdom = ora.infer(target, ev, 4)
+    ref, rdom, kw = oracle_reference(ora, target, ev, 4)
     pdf, dom = bn.infer(target, _t(ev, gpu), N_max=4)
     np.testing.assert_array_equal(dom.cpu().numpy(), rdom)
-    np.testing.assert_allclose(pdf.cpu().numpy(), ref, rtol=RTOL, atol=ATOL)
+    assert_marginals_close(pdf.cpu().numpy(), ref, min_checked_rows=0.45, **kw)
     evt = _t(ev, gpu)
     one, _ = sharded_infer(bn, target, evt, N_max=4)
     np.testing.assert_array_equal(one.cpu().numpy(), pdf.cpu().numpy())
@@ -575,11 +608,15 @@ def test_grid_full_config4_shape_matches_reference_and_oracle(gpu):
     np.testing.assert_array_equal(dom.cpu().numpy(), z["domain"])
     out = pdf.cpu().numpy()
     assert np.isfinite(out).all()
-    np.testing.assert_allclose(out, z["pdf"], rtol=RTOL, atol=ATOL)
+    # both fixtures hold normalised rows only.  Every factor is <= 1, so 1
+    # bounds the unnormalised max from above: a floor of 100 subnormal steps,
+    # tighter than the true max would give.  29 of the 64 queries have a
+    # nonzero row (peaked CPDs: the others meet an unseen parent combination)
+    assert_marginals_close(out, z["pdf"], raw_max=1.0, n_factors=100, min_checked_rows=0.45)
     zr = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "grid10_d64_peaked_ref64.npz"))
     assert list(zr["rows"]) == list(range(64))
     np.testing.assert_array_equal(dom.cpu().numpy()[:1], zr["domain"][:1])
-    np.testing.assert_allclose(out, zr["pdf"], rtol=RTOL, atol=ATOL)
+    assert_marginals_close(out, zr["pdf"], raw_max=1.0, n_factors=100, min_checked_rows=0.45)
     one, _ = sharded_infer(bn, target, ev, N_max=64)
     np.testing.assert_array_equal(one.cpu().numpy(), out)
 
@@ -621,7 +658,8 @@ def test_grid_bench_batch_full_size(gpu):
     r = z["rows"]
     np.testing.assert_allclose(raw[r], z["raw"], rtol=RTOL, atol=0)
     assert z["raw"].max() == z["raw"][list(r).index(int(z["argmax_row"]))].max()
-    np.testing.assert_allclose(out[r], z["raw"] / z["raw"].max(), rtol=RTOL, atol=ATOL)
+    # (the fixture's own unnormalised rows give M; 178 of its 296 rows are nonzero)
+    assert_marginals_close(out[r], z["raw"] / z["raw"].max(), raw_max=float(z["raw"].max()), n_factors=100)
     assert out.max() == 1.0 and np.isfinite(out).all()
     assert gmax > 0 and (raw[r] > 0).any(1).mean() > 0.05
 
@@ -692,9 +730,9 @@ def test_cols_plan_fused_two_rounds(which, Q, gpu):
     np.testing.assert_array_equal(p2.cpu().numpy(), p)
     rstar = int(np.argmax(p.max(1)))
     sub = np.append(np.append(np.arange(0, Q, Q // 40)[:40], [Q - 1]), rstar)
-    ref, _ = OracleBN(edges, cols, data).infer(target, {k: v[sub] for k, v in ev.items()}, N)
+    ref, _, kw = oracle_reference(OracleBN(edges, cols, data), target, {k: v[sub] for k, v in ev.items()}, N)
     assert ref[-1].max() == 1.0
-    np.testing.assert_allclose(p[sub], ref, rtol=RTOL, atol=ATOL)
+    assert_marginals_close(p[sub], ref, **kw)
 
 
 @pytest.mark.parametrize("d,side,Q", [(32, 5, 70001), (64, 4, 40001), (128, 4, 20001)])
@@ -730,9 +768,9 @@ def test_slots_plan_lane_counts_rounds_and_survivors(d, side, Q, gpu):
     rstar = int(np.argmax(p.max(1)))
     sub = np.append(np.append(np.arange(0, Q, Q // 40)[:40], [5, Q - 1]), rstar)
     random.seed(4)
-    ref, _ = OracleBN(edges, cols, data).infer(target, {k: v[sub] for k, v in ev.items()}, d)
+    ref, _, kw = oracle_reference(OracleBN(edges, cols, data), target, {k: v[sub] for k, v in ev.items()}, d)
     assert ref[-1].max() == 1.0
-    np.testing.assert_allclose(p[sub], ref, rtol=RTOL, atol=ATOL)
+    assert_marginals_close(p[sub], ref, **kw)
 
 
 def test_redrawn_domains_reuse_one_plan(gpu):
@@ -749,11 +787,11 @@ def test_redrawn_domains_reuse_one_plan(gpu):
         ev = sample_evidence(data, cols, ["X4", "X2"], 200, 6)
         for seed in (1, 2, 3, 2):
             random.seed(seed)
-            ref, rdom = ora.infer("X5", ev, 7)
+            ref, rdom, kw = oracle_reference(ora, "X5", ev, 7)
             random.seed(seed)
             pdf, dom = bn.infer("X5", _t(ev, gpu), N_max=7)
             np.testing.assert_array_equal(dom.cpu().numpy(), rdom)
-            np.testing.assert_allclose(pdf.cpu().numpy(), ref, rtol=RTOL, atol=ATOL)
+            assert_marginals_close(pdf.cpu().numpy(), ref, **kw)
         kept = [k for k in bn.engine._plans if k[0] == "redrawn"]
         assert len(kept) == 1 and len(bn.engine._plans) == 1
 
@@ -779,8 +817,8 @@ def test_redrawn_domains_on_the_sharded_path(gpu):
             a, adom = bn.infer(target, _t(ev, gpu), N_max=16)
             a = a.clone()
             random.seed(seed)
-            ref, _ = ora.infer(target, ev, 16)
-            np.testing.assert_allclose(a.cpu().numpy(), ref, rtol=RTOL, atol=ATOL)
+            ref, _, kw = oracle_reference(ora, target, ev, 16)
+            assert_marginals_close(a.cpu().numpy(), ref, **kw)
             random.seed(seed)
             b, bdom = sharded_infer(bn, target, _t(ev, gpu), N_max=16)
             np.testing.assert_array_equal(b.cpu().numpy(), a.cpu().numpy())
@@ -871,8 +909,13 @@ def test_grid_free_parent_means_match_reference(name, direct, gpu):
     assert list(z["rows"]) == list(range(meta["Q"]))
     np.testing.assert_array_equal(dom.cpu().numpy()[:1], z["domain"][:1])
     np.testing.assert_array_equal(out > 0, ref > 0)  # same support
-    np.testing.assert_allclose(out, ref, rtol=RTOL, atol=ATOL)
+    # these fixtures hold normalised rows only, and the oracle cannot run them
+    # (4 096 combos per free-parent factor).  Every factor is <= 1, so 1
+    # bounds the unnormalised max from above: a floor of n_factors subnormal
+    # steps, tighter than the true max would give
+    nf = len(nx.ancestors(nx.DiGraph(edges), meta["target"])) + 1
+    assert_marginals_close(out, ref, raw_max=1.0, n_factors=nf)
     nz = ref > 0
     assert np.isfinite(ref).all() and nz.any()
-    # relative agreement on the nonzero marginals themselves (atol aside)
+    # relative agreement on the nonzero marginals themselves (no floor at all)
     assert float(np.max(np.abs(out[nz] - ref[nz]) / ref[nz])) <= RTOL
