@@ -115,6 +115,15 @@ __device__ __forceinline__ float gload_b(const float* p, unsigned byte_off) {
     return *(gfloat_t*)((gchar_t*)p + byte_off);
 }
 
+// A block's max word as the host and the other ranks reduce it: MAX over
+// int32 words (torch.max / the all-reduce).  There a NaN whose sign bit is set
+// is a negative number and loses to every finite max -- and a +NaN evidence
+// value arrives here with its sign flipped (x - mu): the shard with the NaN
+// row was NaN, the other shards stayed finite.  One canonical +NaN instead.
+__device__ __forceinline__ unsigned nan_word(unsigned m) {
+    return (m & 0x7FFFFFFFu) > 0x7F800000u ? 0x7FC00000u : m;
+}
+
 __device__ __forceinline__ unsigned wave_max_u(unsigned v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v = max(v, (unsigned)__shfl_xor((int)v, o, kWave));
@@ -278,11 +287,18 @@ __device__ __forceinline__ f2 tanh_fast2(f2 x) {
 __device__ __forceinline__ float act1(int act, float x) {
     switch (act) {
         case CBN_ACT_TANH: return tanh_fast(x);
-        case CBN_ACT_RELU: return x > 0.f ? x : 0.f;
+        case CBN_ACT_RELU: return x < 0.f ? 0.f : x;  // nn.ReLU: NaN stays NaN, -0.0 stays -0.0
         case CBN_ACT_SIGMOID:  // exp(-x) clamped below FLT_MAX: 1 / (1 + 3.3e38) for x < -88.7 (torch: 0)
             return div_nr(1.f, 1.f + exp_split(-x > 88.7f ? 88.7f : -x));  // NaN stays NaN
         case CBN_ACT_LEAKYRELU: return x > 0.f ? x : x * 0.01f;
-        case CBN_ACT_GELU: return x * 0.5f * (1.f + erff(x * 0.70710678118654752440f));
+        case CBN_ACT_GELU: {
+            // nn.GELU on a float32 CPU tensor halves last: x > FLT_MAX / 2 gives inf, and
+            // +inf gives NaN like -inf (tests/golden/activation_special.npz).  x - x is +0
+            // for a finite x (1 + erf is never -0, so the sum is exact) and NaN for +-inf;
+            // halving last is exact wherever 1 + erf != 1: finite results are unchanged
+            const float t = 1.f + erff(x * 0.70710678118654752440f);
+            return x * (t + (x - x)) * 0.5f;
+        }
         case CBN_ACT_ELU: return x > 0.f ? x : expm1f(x);
         default: return x;
     }
@@ -298,7 +314,7 @@ __device__ __forceinline__ void activate(int act, int w, float (&h)[H]) {
             break;
         case CBN_ACT_RELU:
 #pragma unroll
-            for (int o = 0; o < H; ++o) h[o] = h[o] > 0.f ? h[o] : 0.f;
+            for (int o = 0; o < H; ++o) h[o] = h[o] < 0.f ? 0.f : h[o];
             break;
         case CBN_ACT_LEAKYRELU:
 #pragma unroll
@@ -315,7 +331,7 @@ __device__ __forceinline__ void activate(int act, int w, float (&h)[H]) {
 template <int ACT>
 __device__ __forceinline__ f2 act2(int act, f2 x) {
     if (ACT == CBN_ACT_TANH) return tanh_fast2(x);
-    if (ACT == CBN_ACT_RELU) return f2{x.x > 0.f ? x.x : 0.f, x.y > 0.f ? x.y : 0.f};
+    if (ACT == CBN_ACT_RELU) return f2{x.x < 0.f ? 0.f : x.x, x.y < 0.f ? 0.f : x.y};
     return f2{act1(act, x.x), act1(act, x.y)};
 }
 
@@ -369,7 +385,9 @@ __device__ __forceinline__ float mlp1p(const float* __restrict__ PW, int H, cons
     const int npairs = (H + 1) >> 1;
     float mu = 0.f;
     int P = 0;
-    for (; P + 2 <= npairs; P += 2, PW += 2 * kRec) {
+    // (whole pairs only: the padding unit of an odd H is 0 x z, NaN for an
+    // infinite input, and 0 x NaN must not reach mu -- the tail leaves it out)
+    for (; P + 2 <= (H >> 1); P += 2, PW += 2 * kRec) {
         f2 h[2], w2[2];
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
@@ -385,7 +403,7 @@ __device__ __forceinline__ float mlp1p(const float* __restrict__ PW, int H, cons
         mu = fmaf(w2[1].x, h[1].x, mu);
         mu = fmaf(w2[1].y, h[1].y, mu);
     }
-    if (P < npairs) {
+    for (; P < npairs; ++P, PW += kRec) {  // <= 2 pairs, the last one half for an odd H
         const f2* R = reinterpret_cast<const f2*>(PW);
         f2 a = f2s(0.f);
 #pragma unroll
@@ -394,7 +412,6 @@ __device__ __forceinline__ float mlp1p(const float* __restrict__ PW, int H, cons
         const f2 w2 = R[NIN + 1];
         mu = fmaf(w2.x, h.x, mu);
         if (2 * P + 1 < H) mu = fmaf(w2.y, h.y, mu);
-        PW += kRec;
     }
     return mu + PW[0];
 }
@@ -1188,7 +1205,7 @@ k_param_query(const float* __restrict__ img, int cst_off, int nf, PEv ev, long l
     if (threadIdx.x == 0) {
         unsigned m = 0;
         for (int i = 0; i < wpb; ++i) m = max(m, wm[i]);
-        max_out[blockIdx.x] = m;
+        max_out[blockIdx.x] = nan_word(m);
     }
     if (blockIdx.x == 0)  // words of blocks this launch does not have
         for (int i = (int)gridDim.x + threadIdx.x; i < n_words; i += blockDim.x) max_out[i] = 0u;
@@ -1405,7 +1422,7 @@ __global__ void __launch_bounds__(256) k_param_query_gen(const float* __restrict
     if (threadIdx.x == 0) {
         unsigned m = 0;
         for (int i = 0; i < T / kWave; ++i) m = max(m, wm[i]);
-        max_out[blockIdx.x] = m;
+        max_out[blockIdx.x] = nan_word(m);
     }
     if (blockIdx.x == 0)
         for (int i = (int)gridDim.x + threadIdx.x; i < n_words; i += T) max_out[i] = 0u;

@@ -105,7 +105,8 @@ def _act(name: str, x: np.ndarray) -> np.ndarray:
     if name == "tanh":
         return np.tanh(x)
     if name == "relu":
-        return np.where(x > 0, x, np.float32(0)).astype(np.float32)
+        # nn.ReLU is max(x, 0) with torch's NaN rule: NaN stays NaN, -0.0 stays -0.0
+        return np.where(x < 0, np.float32(0), x).astype(np.float32)
     if name == "sigmoid":
         return (np.float32(1) / (np.float32(1) + np.exp(-x))).astype(np.float32)
     if name == "leakyrelu":
@@ -113,8 +114,14 @@ def _act(name: str, x: np.ndarray) -> np.ndarray:
     if name == "gelu":
         import math
         erf = np.vectorize(math.erf, otypes=[np.float64])
-        return (x * np.float32(0.5) * (np.float32(1) + erf(x * np.float32(0.7071067811865476)).astype(np.float32))
-                ).astype(np.float32)
+        # nn.GELU on a float32 CPU tensor of more than one element (the hidden
+        # layers are [Q, width]), as recorded in tests/golden/
+        # activation_special.npz: the halving comes last, so x > FLT_MAX / 2
+        # gives inf, and +inf gives NaN like -inf (where inf * 0 says so).
+        # Halving is exact wherever 1 + erf is not exactly 1, so every other
+        # value equals x * 0.5 * (1 + erf) bit for bit
+        t = (x * (np.float32(1) + erf(x * np.float32(0.7071067811865476)).astype(np.float32))).astype(np.float32)
+        return np.where(np.isposinf(x), np.float32(np.nan), t * np.float32(0.5)).astype(np.float32)
     if name == "elu":
         return np.where(x > 0, x, np.expm1(x)).astype(np.float32)
     raise KeyError(name)

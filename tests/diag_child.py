@@ -10,6 +10,7 @@ the environment it is testing.  Prints one JSON line.
     python tests/diag_child.py generic   # NN [16] rows: fast kernel vs CBN_PARAM_GENERIC
     python tests/diag_child.py gridfull  # configs[4] bench batch: k_query_slots vs k_query_fast (CBN_NO_SLOTS)
     python tests/diag_child.py gridcoal  # k_query_slots' coalesced index phase vs the per-lane one (CBN_SLOTS_NO_COAL)
+    python tests/diag_child.py coalspecial  # special evidence values: coalesced index phase (CBN_SLOTS_COAL) vs per-lane
 """
 import json
 import os
@@ -103,6 +104,34 @@ def main(mode: str):
         rows = np.append(np.arange(0, 200003, 5003)[:40], [200002, int(np.argmax(outs[0].max(1)))])
         np.save(os.environ["CBN_CHILD_OUT"], outs[0][rows])
         res["rows"] = rows.tolist()
+    elif mode == "coalspecial":
+        # special evidence values (helpers.special_batch) through k_query_slots'
+        # coalesced index phase, forced at a small ragged batch (Q % 4 != 0: the
+        # c4 + e < nv masking) by CBN_SLOTS_COAL=1, vs the per-lane phase:
+        # dense domains and sorted non-integer ones; rows -> CBN_CHILD_OUT
+        from helpers import grid_data, special_batch
+
+        base, cols, edges = grid_data(100000, 7, side=3, d=64, keep=0.995, noise=0)
+        target, names, Q = cols[-1], cols[:-1], 1001
+        res["flags"], res["equal"], res["equal_raw"], keep = [], [], [], {}
+        for tag in ("dense", "levels"):
+            data = base if tag == "dense" else ((np.arange(64) - 2) * 0.25).astype(np.float32)[base.astype(np.int64)]
+            doms = {c: np.unique(data[:, cols.index(c)]) for c in names}
+            ev_np, _ = special_batch(sample_evidence(data, cols, names, Q, 5), doms)
+            ev = {k: torch.tensor(v, device=dev) for k, v in ev_np.items()}
+            bn = make_bn(BayesianNetwork, edges, cols, data, device=dev)
+            outs, raws = [], []
+            for coal in (False, True):  # read per launch
+                os.environ.pop("CBN_SLOTS_COAL", None)
+                if coal:
+                    os.environ["CBN_SLOTS_COAL"] = "1"
+                outs.append(bn.infer(target, ev, N_max=64)[0].cpu().numpy().copy())
+                raws.append(bn.engine.infer_raw(target, ev, 64)[0].cpu().numpy().copy())
+            res["flags"] += [int(lib.cbn_plan_flags(p.handle)) for p in bn.engine._plans.values()]
+            res["equal"].append(bool(np.array_equal(outs[0].view(np.uint32), outs[1].view(np.uint32))))
+            res["equal_raw"].append(bool(np.array_equal(raws[0].view(np.uint32), raws[1].view(np.uint32))))
+            keep[tag] = outs[1]
+        np.savez(os.environ["CBN_CHILD_OUT"], **keep)
     print(json.dumps(res))
 
 

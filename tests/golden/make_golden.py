@@ -170,7 +170,42 @@ CASES = [
     # the oracle reproduces the values
     dict(name="multi_widthN_partial", data=("multi", 2000, 46), target="E",
          ev=["C"], Q=12, N=3, ev_seed=406, width={"C": 3}),
+    # special evidence values (NaN, +-inf, -0.0, subnormals, neighbours of a
+    # domain value, huge values: tests/helpers.special_values) on a chain whose
+    # levels are 0.25 i - 0.5 (0.0 and negative numbers in the domain): the
+    # reference matches with == (brute_force.py:228-237)
+    dict(name="special_bf_chain", data=("chain_stay", 5, 6, 3000, 51, 0.6, [0.25 * i - 0.5 for i in range(6)]), target="X4",
+         ev=["X0", "X1", "X2", "X3"], Q=64, N=6, ev_seed=502, special=True),
 ]
+
+
+def special_evidence(ev, data, cols):
+    """64-query batch for ``special_bf_chain``: the even rows stay on the
+    domain.  Odd rows 1..39: special value (s + 5 c) mod 20 in EVERY column c
+    (each value in each column once).  Odd rows 41..63: one column alone
+    holds -0.0, +0.0 or 0.5 (the special values that are in the domain), on a
+    base row that holds that value there, so those rows keep their support."""
+    sys.path.insert(0, os.path.dirname(HERE))
+    from helpers import special_values
+
+    names = list(ev)
+    vals = {c: special_values(np.unique(data[:, cols.index(c)])) for c in names}
+    nv = len(vals[names[0]])
+    assert nv == 20
+    for s in range(nv):
+        for ci, c in enumerate(names):
+            ev[c][2 * s + 1, 0] = vals[c][(s + 5 * ci) % nv]
+    r = 2 * nv + 1
+    for ci, c in enumerate(names):
+        for k in (4, 5, 14):
+            hit = np.flatnonzero(ev[c][0::2, 0] == vals[c][k])
+            assert hit.size, (c, k)
+            for nm in names:
+                ev[nm][r, 0] = ev[nm][2 * hit[0], 0]
+            ev[c][r, 0] = vals[c][k]
+            r += 2
+    assert r == 65
+    return ev
 
 
 def make_data(spec):
@@ -193,7 +228,7 @@ def make_data(spec):
             return continuous_free_data(spec[1], spec[2])
 
         if spec[0] == "chain_stay":  # bench.py's generator: X_i = X_{i-1} w.p. stay, else uniform
-            return chain_stay(spec[1], spec[2], spec[3], spec[4], stay=spec[5])
+            return chain_stay(spec[1], spec[2], spec[3], spec[4], stay=spec[5], values=spec[6] if len(spec) > 6 else None)
         if spec[0] == "alarm":
             return alarm_like_data(spec[1], spec[2])
         return grid_data(spec[1], spec[2], side=spec[3], d=spec[4], keep=0.9)
@@ -224,6 +259,8 @@ def main():
         for v, k in c.get("width", {}).items():
             ev[v] = np.concatenate([sample_evidence(data, cols, [v], c["Q"], seed=c["ev_seed"] + 1000 * j)[v]
                                     for j in range(k)], 1) if k > 0 else np.zeros((c["Q"], 0), np.float32)
+        if c.get("special"):
+            ev = special_evidence(ev, data, cols)
         ev_t = {k: torch.tensor(v) for k, v in ev.items()}
         if c.get("evidence_none"):
             ev_t = None

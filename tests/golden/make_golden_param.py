@@ -127,7 +127,33 @@ CASES = [
          ev=[f"X{i}" for i in range(49)], Q=32, N=16),
     dict(name="nn_mixed50_config3", est="neural_network", data=("mixed50", 2000, 42), target="X49",
          ev=[f"X{i}" for i in range(49)], Q=32, N=16, model={"hidden_dims": [16], "activation": "tanh"}),
+    # special evidence: ``special`` = the parent column whose rows 5 / 11 / 17
+    # hold NaN / +inf / -inf.  The reference's densities propagate NaN, and
+    # out_pdf.max() (bayesian_network.py:296) spreads it over the batch, so
+    # these fixtures also hold the UNnormalised rows (``raw``)
+    dict(name="special_param_lr", est="linear_regression", data=("chain", 5, 300, 51), target="X4",
+         ev=["X0", "X1", "X2", "X3"], Q=32, N=8, special="X2"),
+    dict(name="special_param_logreg", est="logistic_regression", data=("multi", 400, 52), target="E",
+         ev=["C", "D"], Q=32, N=5, special="C", unit=True),
+    dict(name="special_param_nn_relu", est="neural_network", data=("multi", 400, 53), target="E",
+         ev=["A", "B", "C", "D"], Q=32, N=5, special="C", unit=True,
+         model={"hidden_dims": [16], "activation": "relu"}),
 ]
+SPECIAL_ROWS = {5: np.nan, 11: np.inf, 17: -np.inf}
+
+
+def raw_rows(bn, target, ev_t, N):
+    """The factor product of BayesianNetwork.infer before its division by the
+    batch max (bayesian_network.py:269-293), from the reference's own get_pdf."""
+    import torch
+
+    nodes = bn.get_ancestors(bn.initial_dag, target) + [target]
+    out = None
+    for n in nodes:
+        pdf = bn.get_pdf(n, ev_t, N)[0].to(torch.float32)
+        x = torch.mean(pdf, dim=list(range(1, pdf.dim() - 1)) if pdf.dim() > 2 else [1])
+        out = x.clone() if out is None else out * x
+    return out.numpy().astype(np.float32)
 
 
 def make_data(spec, unit=False):
@@ -185,10 +211,17 @@ def main():
             cfg["model"] = c["model"]
         bn = BayesianNetwork(dag, df, cfg, {"inference_obj": "exact"}, device="cpu")
         ev = sample_evidence(data, cols, c["ev"], c["Q"], seed=200 + i)
+        for r, v in SPECIAL_ROWS.items() if c.get("special") else ():
+            ev[c["special"]][r, 0] = v
         ev_t = {k: torch.tensor(v) for k, v in ev.items()}
         random.seed(c.get("seed", 0))
         p, d = bn.infer(c["target"], ev_t, N_max=c["N"])
         out = dict(data=data, pdf=p.numpy().astype(np.float32), domain=d.numpy().astype(np.float32))
+        if c.get("special"):
+            random.seed(c.get("seed", 0))
+            out["raw"] = raw_rows(bn, c["target"], ev_t, c["N"])
+            assert np.array_equal((torch.tensor(out["raw"]) / torch.tensor(out["raw"]).max()).numpy(), out["pdf"],
+                                  equal_nan=True), c["name"]
         meta_params = {}
         for n in cols:
             layers, ls = _params(bn.nodes_obj[n].estimator)

@@ -44,7 +44,8 @@ def param_golden_names():
 def load_param_golden(name):
     """Fixture of tests/golden/make_golden_param.py: data, evidence, the
     reference's outputs and every node's fitted parameters
-    (params[node] = ([(W, b), ...], log_scale))."""
+    (params[node] = ([(W, b), ...], log_scale)); ``raw`` where the fixture
+    holds the reference's unnormalised rows."""
     z = np.load(os.path.join(GOLDEN_DIR, name + ".npz"), allow_pickle=False)
     meta = json.loads(str(z["meta"]))
     ev = {k[3:]: z[k] for k in z.files if k.startswith("ev_")}
@@ -52,7 +53,10 @@ def load_param_golden(name):
     for n, pm in meta["params"].items():
         layers = [(z[f"W_{n}_{i}"], z[f"b_{n}_{i}"]) for i in range(pm["n_layers"])]
         params[n] = (layers, pm["log_scale"])
-    return dict(meta=meta, data=z["data"], pdf=z["pdf"], domain=z["domain"], evidence=ev, params=params)
+    g = dict(meta=meta, data=z["data"], pdf=z["pdf"], domain=z["domain"], evidence=ev, params=params)
+    if "raw" in z.files:  # the special-evidence fixtures: the reference's unnormalised rows
+        g["raw"] = z["raw"]
+    return g
 
 
 FAMILY = {"linear_regression": "gauss", "logistic_regression": "logistic", "neural_network": "logistic"}

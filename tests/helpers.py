@@ -108,6 +108,54 @@ def sample_evidence(data, cols, names, Q, seed, missing_frac=0.0, missing_value=
     return ev
 
 
+def special_values(dom):
+    """The special evidence values for one column whose fitted domain is
+    ``dom`` (sorted float32): the floats an index search can get wrong.  The
+    reference matches evidence with IEEE ``==`` (brute_force.py:228-237): NaN
+    and +-inf match nothing, -0.0 matches a fitted 0.0."""
+    f = np.float32
+    dom = np.asarray(dom, np.float32)
+    v = dom[dom != 0][len(dom) // 2 - 1]  # a nonzero domain value
+    nan, sub = f(np.nan), f(2.0 ** -149)
+    out = [nan, np.copysign(nan, f(-1)), f(np.inf), f(-np.inf), f(-0.0), f(0.0), sub, -sub,
+           np.nextafter(v, f(np.inf)), np.nextafter(v, f(-np.inf)), dom[0] - f(3.0), dom[-1] + f(2.5), f(len(dom)),
+           f(-1.0), f(0.5), f(16777217.0), f(2147483648.0), f(4294967296.0), f(3e38), f(-3e38)]
+    return np.array(out, np.float32)
+
+
+def special_batch(ev, doms):
+    """``ev`` (on-domain evidence, {column: [Q, 1]}) with special values written
+    in: special row s = (column c, value k of ``special_values(doms[c])``) sits
+    at row 2 s + 1 and differs from a clean row in column c alone, so that
+    column decides it; every (column, value) pair occurs; the even rows and
+    everything past the last special row stay clean (Q >= 4 x columns x
+    values keeps half of the batch clean).  Where the value is in the domain
+    under ``==`` (+-0.0, 0.5, ...) the row's base is a clean row that holds
+    that value in column c (if the batch has one), so the row has support; the
+    +0.0 row shares the -0.0 row's base.  Returns (evidence, rows) with rows =
+    [(row, column, k, value, on_domain)]."""
+    names = list(ev)
+    Q = ev[names[0]].shape[0]
+    out = {k: np.array(v, np.float32, copy=True) for k, v in ev.items()}
+    rows = []
+    s = b = 0
+    for c in names:
+        vals = special_values(doms[c])
+        for k, val in enumerate(vals):
+            r = 2 * s + 1
+            assert r < Q, "batch too small for the special rows"
+            on = bool((np.asarray(doms[c], np.float32) == val).any())
+            # clean rows are the even ones: a base row that already holds this value in column c
+            hit = np.flatnonzero(ev[c][::2, 0] == val) if on else np.zeros(0, np.int64)
+            b = b if k == 5 else 2 * int(hit[0]) if hit.size else r  # (k = 5: +0.0 after -0.0)
+            for nm in names:
+                out[nm][r, 0] = ev[nm][b, 0]
+            out[c][r, 0] = val
+            rows.append((r, c, k, val, on))
+            s += 1
+    return out, rows
+
+
 def alarm_like_data(S, seed, n=37, d=8, max_parents=4, n_edges=46):
     """ALARM-shaped synthetic network (BASELINE configs[2]): n nodes, n_edges
     edges, in-degree <= max_parents, card d.  Edges go from lower to higher

@@ -285,12 +285,14 @@ def assert_golden_close(got, name, param=False, got_raw=None, **kw):
     unnormalised rows (``got_raw``) with the oracle's."""
     from golden_io import load_golden, load_param_golden
 
-    ref = (load_param_golden(name) if param else load_golden(name))["pdf"]
+    g = load_param_golden(name) if param else load_golden(name)
+    ref = g["pdf"]
     mx, nf, pk = golden_scale(name, param)
     if np.isnan(ref).any():
         assert got_raw is not None, f"{name}: a NaN fixture needs the unnormalised rows"
+        # (the reference's own unnormalised rows where the fixture holds them, else the oracle's)
         assert_marginals_close(got, ref, raw_max=mx, n_factors=nf, peak=pk, nan="match", got_raw=got_raw,
-                               ref_raw=golden_raw(name, param), **kw)
+                               ref_raw=g["raw"] if "raw" in g else golden_raw(name, param), **kw)
     else:
         kw.setdefault("min_checked_rows", MIN_CHECKED_ROWS.get(name, 0.5))
         assert_marginals_close(got, ref, raw_max=mx, n_factors=nf, peak=pk, **kw)

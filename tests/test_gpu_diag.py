@@ -83,3 +83,35 @@ def test_grid_coalesced_index_phase_equals_per_lane(gpu, tmp_path):
     ref, _, kw = oracle_reference(OracleBN(edges, cols, data), target, {k: v[rows] for k, v in ev.items()}, 64)
     got = np.load(outp)
     assert_marginals_close(got / got.max(), ref, **kw)
+
+
+def test_special_evidence_through_coalesced_index_phase(gpu, tmp_path):
+    """Special evidence values (NaN, +-inf, -0.0, ... tests/helpers.py
+    special_batch) through k_query_slots' coalesced index phase -- 16-B
+    evidence loads, two int16 indices packed per word -- forced at 1 001
+    queries (not a multiple of 4: the tail masking) by CBN_SLOTS_COAL=1 under
+    CBN_DIAG=1: bit for bit the per-lane phase's rows (normalised and raw),
+    for dense and for sorted non-integer domains; every row whose special
+    value == no domain entry is exactly zero, and -0.0 rows equal +0.0 rows."""
+    import numpy as np
+
+    from helpers import grid_data, sample_evidence, special_batch
+
+    outp = str(tmp_path / "rows.npz")
+    res, _ = _child("coalspecial", CBN_DIAG="1", CBN_CHILD_OUT=outp)  # (the child sets CBN_SLOTS_COAL per launch)
+    assert res["diag"] == 1
+    assert res["equal"] == [True, True] and res["equal_raw"] == [True, True]
+    assert len(res["flags"]) == 2 and all(f & _native.CBN_PLAN_SLOTS for f in res["flags"])
+    base, cols, edges = grid_data(100000, 7, side=3, d=64, keep=0.995, noise=0)
+    z = np.load(outp)
+    for tag in ("dense", "levels"):
+        data = base if tag == "dense" else ((np.arange(64) - 2) * 0.25).astype(np.float32)[base.astype(np.int64)]
+        doms = {c: np.unique(data[:, cols.index(c)]) for c in cols[:-1]}
+        ev, rows = special_batch(sample_evidence(data, cols, cols[:-1], 1001, 5), doms)
+        p = z[tag]
+        off = [r[0] for r in rows if not r[4]]
+        assert p.shape == (1001, 64) and p.max() == 1.0 and len(off) >= 17 * 8 and (p[off] == 0).all()
+        for c in cols[:-1]:
+            r_neg, r_pos = (next(r[0] for r in rows if r[1] == c and r[2] == k) for k in (4, 5))
+            np.testing.assert_array_equal(p[r_neg].view(np.uint32), p[r_pos].view(np.uint32))
+        assert any((p[r[0]] > 0).any() for r in rows if r[4])

@@ -579,3 +579,152 @@ def test_split_order_guard_quiet_case(gpu):
     off = rng.uniform(-0.02, 0.02, (_GUARD_N, Q)).astype(np.float32)
     ref_raw = _guard_check(bn, ora, _guard_evidence(cols, Q, off), gpu)
     assert (ref_raw[:, 7] > 2.0 ** -100).all()
+
+
+# ---------------------------------------------------------------------------
+# Special evidence values through the parametric kernels.  The reference's
+# densities are plain float arithmetic: a NaN parent value gives a NaN mean and
+# a NaN row, +-inf gives a zero Gaussian (exp(-inf)) and NaN or 0 for the
+# logistic density, and out_pdf.max() (bayesian_network.py:296) spreads one NaN
+# over the whole batch.  The oracle is pinned to the reference on these inputs
+# by tests/golden/activation_special.npz and special_param_*.npz; here the
+# kernels are compared with it on the same parameters: NaN / inf positions of
+# the UNnormalised rows equal, finite values at rtol 1e-5, every untouched row
+# bit-identical to the same row of the clean batch.
+SPECIAL_ROWS = ((50, np.nan), (100, np.inf), (150, -np.inf))
+
+
+def _special_param_check(bn, ora, target, ev, clean, N, gpu, expect_nan=True):
+    from continuousbayesiannetwork_amd import _native
+
+    eng = bn.engine
+    res = eng.infer_raw(target, _t(ev, gpu), N)
+    assert res is not None
+    raw, words = res[0].cpu().numpy().copy(), res[2].clone()
+    out = res[3](res[0], words).cpu().numpy().copy()
+    flags = [_native.load().cbn_plan_flags(p.handle) for p in eng._plans.values()]
+    assert flags and all(f & _native.CBN_PLAN_PARAMETRIC for f in flags)
+    raw_clean = eng.infer_raw(target, _t(clean, gpu), N)[0].cpu().numpy().copy()
+    with np.errstate(all="ignore"):
+        ref_raw, _ = ora.infer_raw(target, ev, N)
+        ref = (ref_raw / ref_raw.max()).astype(np.float32)
+    kw = dict(raw_max=float(ref_raw.max()), n_factors=n_factors(ora, target), peak=oracle_peak(ora, target))
+    assert bool(np.isnan(ref_raw).any()) == expect_nan
+    if expect_nan:
+        assert np.isnan(ref).all()  # one NaN row: the batch max, and so every entry
+        assert_marginals_close(out, ref, nan="match", got_raw=raw, ref_raw=ref_raw, **kw)
+        assert np.isnan(out).all()
+    else:
+        assert np.isfinite(raw).all()
+        assert_marginals_close(out, ref, **kw)
+    pdf, _ = bn.infer(target, _t(ev, gpu), N_max=N)  # the fused / two-pass path
+    np.testing.assert_array_equal(np.isnan(pdf.cpu().numpy()), np.isnan(ref))
+    touched = np.zeros(raw.shape[0], bool)
+    for k in ev:
+        touched |= ~((ev[k] == clean[k]).all(1))  # (NaN != NaN: a NaN row counts as touched)
+    assert 0 < touched.sum() <= 16
+    np.testing.assert_array_equal(raw[~touched].view(np.uint32), raw_clean[~touched].view(np.uint32))
+    assert np.isfinite(raw_clean).all() and (raw_clean > 0).any(1).mean() > 0.9
+    return raw, ref_raw
+
+
+# [16]: the pair-packed one-hidden-layer form; [7]: an odd width (a padding unit
+# in the last pair, 0 x inf there must not reach mu); [8, 8]: the multi-layer
+# register form; [33, 4]: beyond the register-resident kernels (k_param_query_gen)
+@pytest.mark.parametrize("hidden", [[16], [7], [8, 8], [33, 4]], ids=["h16", "h7", "h8x8", "h33x4"])
+@pytest.mark.parametrize("act", ["relu", "tanh", "sigmoid", "leakyrelu", "gelu", "elu"])
+def test_special_evidence_through_activations(act, hidden, gpu):
+    data, cols, edges = mixed_dag_data(1500, 4, n=6, unit=True)
+    bn = make_bn(BayesianNetwork, edges, cols, data, device=gpu, estimator="neural_network",
+                 config=param_config("neural_network", n_epochs=5, model={"hidden_dims": hidden, "activation": act}))
+    ora = _oracle_from_bn(bn, edges, cols, data, "neural_network", act)
+    clean = sample_evidence(data, cols, cols[:-1], 256, 3)
+    ev = {k: v.copy() for k, v in clean.items()}
+    for r, v in SPECIAL_ROWS:
+        ev[cols[-2]][r, 0] = v  # X4 -> X5 (the backbone edge): the target's own factor reads it
+    raw, ref_raw = _special_param_check(bn, ora, cols[-1], ev, clean, 8, gpu)
+    assert np.isnan(ref_raw[50]).all() and np.isnan(raw[50]).all()
+
+
+@pytest.mark.parametrize("k,n_obs", [(1, 1), (3, 3), (4, 4), (5, 5), (2, 1), (3, 1)])
+def test_special_evidence_linear_regression_parents(k, n_obs, gpu):
+    """A LinearRegression node with k parents (1, 3, 4: the zero-padded
+    4-input weights and the column table's null pointers; 5: beyond them), one
+    parent special and the others finite; n_obs < k: free parents beside the
+    observed special one (the per-combo inputs).  +-inf evidence: the Gaussian
+    is exactly 0 (exp(-inf)) and the rest of the batch stays finite."""
+    rng = np.random.default_rng(40 + k)
+    S, Q, N = 3000, 256, 8
+    R = np.round(rng.normal(0, 1, (S, k)), 2)
+    Y = np.round(R @ rng.uniform(0.3, 0.8, k) + rng.normal(0, 0.5, S), 2)
+    data = np.concatenate([R, Y[:, None]], 1).astype(np.float32)
+    cols = [f"R{i}" for i in range(k)] + ["Y"]
+    edges = [(f"R{i}", "Y") for i in range(k)]
+    bn = make_bn(BayesianNetwork, edges, cols, data, device=gpu, estimator="linear_regression",
+                 config=param_config("linear_regression", n_epochs=20))
+    ora = _oracle_from_bn(bn, edges, cols, data, "linear_regression")
+    assert (bn.nodes_obj["Y"].estimator.linear_model.weight.detach().cpu().numpy() != 0).all()  # (w x inf = +-inf)
+    clean = sample_evidence(data, cols, cols[:n_obs], Q, 6)
+    inf_only = {c: v.copy() for c, v in clean.items()}
+    for i in range(n_obs):  # each observed parent in turn
+        inf_only[cols[i]][100 + i, 0] = np.inf
+        inf_only[cols[i]][150 + i, 0] = -np.inf
+    raw, ref_raw = _special_param_check(bn, ora, "Y", inf_only, clean, N, gpu, expect_nan=False)
+    hit = [100 + i for i in range(n_obs)] + [150 + i for i in range(n_obs)]
+    assert (raw[hit] == 0).all() and (ref_raw[hit] == 0).all()
+    ev = {c: v.copy() for c, v in inf_only.items()}
+    for i in range(n_obs):
+        ev[cols[i]][50 + i, 0] = np.nan if i % 2 == 0 else np.copysign(np.float32(np.nan), np.float32(-1))
+    raw, ref_raw = _special_param_check(bn, ora, "Y", ev, clean, N, gpu)
+    assert np.isnan(raw[50:50 + n_obs]).all() and (raw[hit] == 0).all()
+
+
+def test_split_order_guard_nan_row(gpu):
+    """The 4-part split with its order guard (the quiet case's chain): one
+    query's evidence is NaN.  That row is NaN; the guard decides per row, so
+    every other row's unnormalised values are those of the clean batch."""
+    sig = [1.0] + [0.05] * 12 + [1.0] * (_GUARD_N - 13)
+    bn, ora, cols = _guard_chain(gpu, sig)
+    Q = 512
+    rng = np.random.default_rng(8)
+    off = rng.uniform(-0.02, 0.02, (_GUARD_N, Q)).astype(np.float32)
+    clean = _guard_evidence(cols, Q, off)
+    for col, row, v in ((cols[10], 77, np.nan), (cols[3], 300, np.copysign(np.float32(np.nan), np.float32(-1)))):
+        ev = {k: a.copy() for k, a in clean.items()}
+        ev[col][row, 0] = v
+        raw, ref_raw = _special_param_check(bn, ora, cols[-1], ev, clean, 16, gpu)
+        assert np.isnan(raw[row]).all() and np.isfinite(np.delete(raw, row, 0)).all()
+
+
+@pytest.mark.parametrize("negative", [False, True], ids=["nan", "negative_nan"])
+def test_sharded_raw_path_with_a_nan_row(negative, gpu):
+    """sharded_infer's raw path, one rank over 3 ragged shards, the NaN row in
+    the middle shard: the NaN max word wins the MAX over the shards' int32
+    words (a NaN with its sign bit set included) and reaches the scale, so
+    every shard's rows are NaN, as the single call's are."""
+    from continuousbayesiannetwork_amd.distributed import shard_evidence, sharded_infer
+
+    data, cols, edges = mixed_dag_data(4000, 6, n=16)
+    bn = make_bn(BayesianNetwork, edges, cols, data, device=gpu, estimator="linear_regression",
+                 config=param_config("linear_regression", n_epochs=10))
+    Q = 1001
+    ev = sample_evidence(data, cols, cols[:-1], Q, 11)
+    ev[cols[-2]][500, 0] = np.copysign(np.float32(np.nan), np.float32(-1)) if negative else np.nan
+    evt = _t(ev, gpu)
+    full = bn.infer(cols[-1], evt, N_max=16)[0].clone()
+    assert torch.isnan(full).all()
+    rows, bits, scales = [], [], []
+    for r in range(3):
+        o, _, b, sc = bn.engine.infer_raw(cols[-1], shard_evidence(evt, 3, r), 16)
+        rows.append(o.clone())
+        bits.append(b.clone())
+        scales.append(sc)
+    assert [o.shape[0] for o in rows] != [Q // 3] * 3 and sum(o.shape[0] for o in rows) == Q
+    assert torch.isfinite(rows[0]).all() and torch.isfinite(rows[2]).all() and torch.isnan(rows[1]).any()
+    m = torch.stack(bits).max(0).values  # the all-reduce's MAX over int32 words
+    for o, sc in zip(rows, scales):
+        sc(o, m)
+        assert torch.isnan(o).all()
+    np.testing.assert_array_equal(torch.cat(rows).cpu().numpy(), full.cpu().numpy())  # (NaN == NaN here)
+    one, _ = sharded_infer(bn, cols[-1], evt, N_max=16)
+    np.testing.assert_array_equal(one.cpu().numpy(), full.cpu().numpy())

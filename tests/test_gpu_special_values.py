@@ -1,0 +1,323 @@
+"""Special evidence values -- NaN of both signs, +-inf, -0.0, subnormals, the
+float neighbours of a domain value, values at and beyond the domain's ends,
+2^24 + 1, 2^31, 2^32, +-3e38 (tests/helpers.special_values) -- through every
+copy of the evidence -> domain-index mapping of the BruteForce kernels.
+
+The reference matches evidence with IEEE ``==`` (brute_force.py:228-237): a
+value that equals no domain entry gives a zero row, -0.0 matches a fitted 0.0.
+Expected values: the CPU oracle (pinned to the reference on these inputs by
+tests/golden/special_bf_chain.npz), exact zeros for the rows ``==`` leaves
+unmatched, and bit-identity -- of the -0.0 row with the +0.0 row, of every
+untouched row with the same row of the clean batch (a special value must not
+reach its wave- and block-mates), and of the launch forms with each other.
+Every case asserts the kernel it reaches by ``cbn_plan_flags``.
+"""
+import random
+
+import networkx as nx
+import numpy as np
+import pytest
+import torch
+
+from continuousbayesiannetwork_amd import BayesianNetwork, BruteForce, Node, _native
+from continuousbayesiannetwork_amd.inference.engine import domain_index, domain_index_host
+from helpers import (alarm_like_data, chain_data, grid_data, make_bn, sample_evidence, special_batch,
+                     special_values)
+from oracle.ref_infer import OracleBN, OracleBruteForce, OracleNode
+from parity import assert_factor_close, assert_marginals_close, oracle_reference
+
+pytestmark = pytest.mark.gpu
+
+FAST, LDS, PAIRED, STAGED = _native.CBN_PLAN_FAST, _native.CBN_PLAN_LDS, _native.CBN_PLAN_PAIRED, _native.CBN_PLAN_STAGED
+DIRECT, COLS, SLOTS = _native.CBN_PLAN_DIRECT, _native.CBN_PLAN_COLS, _native.CBN_PLAN_SLOTS
+
+
+def _t(ev, dev):
+    return {k: torch.tensor(v, device=dev) for k, v in ev.items()}
+
+
+def _bits(a):
+    return np.ascontiguousarray(a, np.float32).view(np.uint32)
+
+
+def levels(d):
+    """A sorted non-integer domain with 0.0 and negative values: -0.5, -0.25, 0.0, 0.25, ..."""
+    return ((np.arange(d) - 2) * 0.25).astype(np.float32)
+
+
+def _remap(data, dense):
+    """Integer levels 0..d-1 (the kernels' dense shortcut) or ``levels`` (their binary search)."""
+    if dense:
+        return data
+    idx = data.astype(np.int64)
+    return levels(int(idx.max()) + 1)[idx]
+
+
+def _star(k, d, S, seed):
+    rng = np.random.default_rng(seed)
+    P = rng.integers(0, d, (S, k))
+    C = (P.sum(1) + rng.integers(0, 3, S)) % d
+    cols = [f"P{i}" for i in range(k)] + ["C"]
+    return np.concatenate([P, C[:, None]], 1).astype(np.float32), cols, [(f"P{i}", "C") for i in range(k)]
+
+
+def _chain_with_small_root(S, seed):
+    """X0 -> ... -> X4 over 32 levels plus a 4-level root R -> X3: X3's table
+    has two observed parents (4 x 32 rows, inside the paired layout's LDS
+    share).  N = 32 > |R|: R's sample domain is padded per call (redrawn plan)."""
+    data, cols, edges = chain_data(5, 32, S, seed, stay=0.8)
+    rng = np.random.default_rng(seed + 1)
+    R = rng.integers(0, 4, S)
+    X = data.astype(np.int64)
+    X[:, 3] = (X[:, 3] + R) % 32
+    X[:, 4] = np.where(rng.random(S) < 0.8, X[:, 3], rng.integers(0, 32, S))
+    return np.concatenate([X, R[:, None]], 1).astype(np.float32), cols + ["R"], edges + [("R", "X3")]
+
+
+# name -> (data builder, target, N, Q, flags wanted, flags forbidden, oracle on a row subset, random seed)
+CASES = {
+    # k_query, scalar stores (N = 5: not a multiple of 4)
+    "query_scalar": (lambda: chain_data(5, 5, 4000, 11, stay=0.7), "X4", 5, 400, 0, FAST | DIRECT, False, None),
+    # k_query, vector stores: the fast gate declines a factor with more than kFastObs = 4 observed parents
+    "query_vector": (lambda: _star(5, 4, 20000, 3), "C", 4, 420, 0, FAST | DIRECT, False, None),
+    # k_query_fast: tables in LDS, N = 64 (8 lanes per query: not paired, no column / slot staging)
+    "fast_lds": (lambda: chain_data(4, 64, 40000, 12, stay=0.8), "X3", 64, 129, FAST | LDS,
+                 PAIRED | STAGED | COLS | SLOTS, False, None),
+    # k_query_cols over the LDS image, 1 and 2 lanes per query
+    "cols8_lds": (lambda: chain_data(6, 8, 8000, 13, stay=0.7), "X5", 8, 420, FAST | LDS | COLS, STAGED | SLOTS,
+                  False, None),
+    "cols16_lds": (lambda: chain_data(5, 16, 20000, 14, stay=0.8), "X4", 16, 333, FAST | LDS | COLS, STAGED | SLOTS,
+                   False, None),
+    # k_query_cols over the global-table image (configs[2]'s plan: 8^4-row tables)
+    "cols_global": (lambda: alarm_like_data(50000, 5), "X35", 8, 1601, FAST | COLS, LDS | STAGED | SLOTS, True, None),
+    # k_query_slots, per-lane index phase (one block round: the coalesced phase needs >= 3)
+    "slots": (lambda: grid_data(100000, 7, side=3, d=64, keep=0.995, noise=0), "X8", 64, 1001, FAST | SLOTS,
+              LDS | STAGED | COLS, True, None),
+    # k_query_staged: one observed parent per factor (dense: the shortcut; levels: the general
+    # branch's binary search), more than one 128-query unit and a ragged end
+    "staged": (lambda: chain_data(6, 32, 30000, 15, stay=0.8), "X5", 32, 421, FAST | LDS | PAIRED | STAGED,
+               COLS | SLOTS, False, None),
+    # k_query_staged: a factor with two observed parents (the second evidence load)
+    "staged_two_parents": (lambda: _chain_with_small_root(30000, 16), "X4", 32, 421, FAST | LDS | PAIRED | STAGED,
+                           COLS | SLOTS, False, 7),
+}
+
+
+def _plan_flags(bn):
+    lib = _native.load()
+    return [int(lib.cbn_plan_flags(p.handle)) for p in bn.engine._plans.values()]
+
+
+def _ancestors(edges, target):
+    return sorted(nx.ancestors(nx.DiGraph(edges), target))
+
+
+def check_special(bn, ora, data, cols, target, names, N, Q, gpu, want, forbid, subset, rseed, ev_seed=5):
+    """The five assertions of the module docstring on one plan."""
+    eng = bn.engine
+
+    def seeded(fn, *a, **kw):
+        random.seed(rseed)
+        return fn(*a, **kw)
+
+    doms = {c: np.unique(data[:, cols.index(c)]) for c in names}
+    clean = sample_evidence(data, cols, names, Q, ev_seed)
+    ev, rows = special_batch(clean, doms)
+    special = np.array([r[0] for r in rows])
+    untouched = np.ones(Q, bool)
+    untouched[special] = False
+    assert untouched.mean() >= 0.5
+    evt, cleant = _t(ev, gpu), _t(clean, gpu)
+
+    eng.fused = True
+    pdf, dom = seeded(bn.infer, target, evt, N_max=N)
+    p = pdf.cpu().numpy().copy()
+    flags = _plan_flags(bn)
+    assert len(flags) == 1 and flags[0] & want == want and not flags[0] & forbid, f"plan flags {flags}"
+    assert np.isfinite(p).all() and p.max() == 1.0
+
+    # 1. the oracle (a row subset with the batch argmax row last, for the plans it cannot run whole)
+    on = np.array([r[0] for r in rows if r[4]], np.int64)
+    off = np.array([r[0] for r in rows if not r[4]], np.int64)
+    if subset:
+        even = np.arange(0, Q, 2)
+        sub = np.concatenate([on, off[::7], even[:: max(1, len(even) // 96)][:96], [int(np.argmax(p.max(1)))]])
+    else:
+        sub = np.arange(Q)
+    ref, rdom, kw = seeded(oracle_reference, ora, target, {k: v[sub] for k, v in ev.items()}, N)
+    if subset:
+        assert ref[-1].max() == 1.0  # the same normaliser on both sides
+    d = dom.cpu().numpy()
+    np.testing.assert_array_equal(d[sub] if d.shape[0] == Q else d, rdom)
+    assert_marginals_close(p[sub], ref, **kw)
+
+    # 2. a value that == no domain entry: the row is exactly zero
+    assert off.size >= 17 * len(names) and (p[off] == 0).all()
+    assert (ref[np.isin(sub, off)] == 0).all()
+
+    # 3. -0.0 and +0.0 (same base row): bit-identical rows; nonzero where 0.0 is in the domain
+    live = 0
+    for c in names:
+        r_neg, r_pos = (next(r[0] for r in rows if r[1] == c and r[2] == k) for k in (4, 5))
+        assert np.signbit(ev[c][r_neg, 0]) and not np.signbit(ev[c][r_pos, 0]) and ev[c][r_pos, 0] == 0
+        np.testing.assert_array_equal(_bits(p[r_neg]), _bits(p[r_pos]))
+        live += int((p[r_neg] > 0).any())
+    assert live > 0 or not any((doms[c] == 0).any() for c in names)
+
+    # 4. row independence: every untouched row equals, bit for bit, the same row of the clean batch --
+    # unnormalised (the raw launch), or normalised by one fixed max word (the two-pass write) where the
+    # plan takes no raw launch
+    res = seeded(eng.infer_raw, target, evt, N)
+    if res is not None:
+        raw = res[0].cpu().numpy().copy()
+        words = res[2].clone()
+        scaled = res[3](res[0], words).cpu().numpy().copy()
+        raw_clean = seeded(eng.infer_raw, target, cleant, N)[0].cpu().numpy()
+        # 5b. the raw launch + cbn_scale == the fused launch
+        np.testing.assert_array_equal(_bits(scaled), _bits(p))
+    else:
+        plan, cc, nq, _, dev = seeded(eng.prepare, target, cleant, N)
+        bits = eng.query_max(plan, cc, nq, dev).clone()
+        raw_clean = eng.query_write(plan, cc, nq, bits, torch.empty((nq, N), device=dev), dev).cpu().numpy().copy()
+        plan, cs, nq, _, dev = seeded(eng.prepare, target, evt, N)
+        raw = eng.query_write(plan, cs, nq, bits, torch.empty((nq, N), device=dev), dev).cpu().numpy().copy()
+    np.testing.assert_array_equal(_bits(raw[untouched]), _bits(raw_clean[untouched]))
+    assert (raw_clean[untouched] > 0).any(1).mean() > 0.05
+
+    # 5a. the two-pass launch == the fused launch
+    eng.fused = False
+    p2, _ = seeded(bn.infer, target, evt, N_max=N)
+    np.testing.assert_array_equal(_bits(p2.cpu().numpy()), _bits(p))
+    eng.fused = True
+    return p
+
+
+@pytest.mark.parametrize("dense", [True, False], ids=["dense", "levels"])
+@pytest.mark.parametrize("case", list(CASES))
+def test_special_evidence_through_table_kernels(case, dense, gpu):
+    build, target, N, Q, want, forbid, subset, rseed = CASES[case]
+    data, cols, edges = build()
+    data = _remap(data, dense)
+    names = _ancestors(edges, target)
+    bn = make_bn(BayesianNetwork, edges, cols, data, device=gpu)
+    check_special(bn, OracleBN(edges, cols, data), data, cols, target, names, N, Q, gpu, want, forbid, subset, rseed)
+
+
+@pytest.mark.parametrize("dense", [True, False], ids=["dense", "levels"])
+@pytest.mark.parametrize("how", ["forced_direct", "hashed"])
+def test_special_evidence_through_direct_plans(how, dense, gpu):
+    """``bsearch_dom`` (cbn_direct.hip) under the direct keys: the small chain
+    on a forced direct plan, and with every CPD hashed (dense_limit = 1)."""
+    data, cols, edges = chain_data(5, 5, 4000, 11, stay=0.7)
+    data = _remap(data, dense)
+    bn = make_bn(BayesianNetwork, edges, cols, data, device=gpu)
+    if how == "forced_direct":
+        bn.engine.force_direct = True
+    else:
+        for nd in bn.nodes_obj.values():
+            nd.estimator.dense_limit = 1
+    check_special(bn, OracleBN(edges, cols, data), data, cols, "X4", cols[:4], 5, 400, gpu, DIRECT, FAST, False, None)
+    if how == "hashed":
+        assert all(nd.estimator.sparse for nd in bn.nodes_obj.values() if nd.estimator.n_cells() > 1)
+
+
+@pytest.mark.parametrize("dense", [True, False], ids=["dense", "levels"])
+def test_special_values_in_wide_columns(dense, gpu):
+    """A [Q, N] evidence column (N per-query values of the parent C, read per
+    (query, combo) by the wide direct plan) whose values include the special
+    list: each special value zeroes its own combos only; vs the oracle."""
+    rng = np.random.default_rng(3)
+    S, d, N, Q = 6000, 4, 4, 400
+    A, B = rng.integers(0, d, S), rng.integers(0, d, S)
+    C = (A + B + rng.integers(0, 2, S)) % d
+    D = (A + rng.integers(0, 2, S)) % d
+    E = (C + D + rng.integers(0, 2, S)) % d
+    data = _remap(np.stack([A, B, C, D, E], 1).astype(np.float32), dense)
+    cols, edges = ["A", "B", "C", "D", "E"], [("A", "C"), ("B", "C"), ("C", "E"), ("D", "E"), ("A", "D")]
+    dom = np.unique(data[:, 2])
+    vals = special_values(dom)
+    cw = dom[rng.integers(0, d, (Q, N))]
+    for k, v in enumerate(vals):  # special value k in row 2 k + 1, at sample position k % N
+        cw[2 * k + 1, k % N] = v
+    ev = {"C": cw}
+    bn = make_bn(BayesianNetwork, edges, cols, data, device=gpu)
+    ref, rdom, kw = oracle_reference(OracleBN(edges, cols, data), "E", ev, N)
+    for _ in range(2):  # the second call: the cached wide plan
+        pdf, dm = bn.infer("E", _t(ev, gpu), N_max=N)
+        np.testing.assert_array_equal(dm.cpu().numpy(), rdom)
+        assert_marginals_close(pdf.cpu().numpy(), ref, **kw)
+    wide = [wp for _, wp in bn.engine._wide_plans.values()]  # the wide direct plan served the calls
+    assert len(wide) == 1 and _native.load().cbn_plan_flags(wide[0].handle) & DIRECT
+    allsp = cw.copy()
+    allsp[1] = vals[:N]  # every combo of the row off the domain (NaN, NaN, inf, -inf): a zero row
+    p, _ = bn.infer("E", _t({"C": allsp}, gpu), N_max=N)
+    assert (p.cpu().numpy()[1] == 0).all()
+
+
+@pytest.mark.parametrize("dense", [True, False], ids=["dense", "levels"])
+@pytest.mark.parametrize("hashed", [False, True], ids=["dense_cpd", "hashed_cpd"])
+def test_special_values_in_get_prob(hashed, dense, gpu):
+    """BruteForce.get_prob (k_cpd_eval; hashed: k_cpd_ref_eval) and
+    Node.get_prob with the special list in the evaluated points and in the
+    parent query: vs the oracle, exact zeros at every unmatched value."""
+    rng = np.random.default_rng(0)
+    S, d = 5000, 5
+    pd_ = _remap(rng.integers(0, d, (2, S)).astype(np.float32), dense)
+    lv = np.unique(pd_)
+    nd_ = lv[(rng.integers(0, d, S) + rng.integers(0, 2, S)) % d]
+    kw = {"dense_limit": 1} if hashed else {}
+    ob = OracleBruteForce()
+    ob.fit(nd_, pd_)
+    bf = BruteForce({"estimator_name": "brute_force"}, device=gpu, **kw)
+    bf.fit(torch.tensor(nd_, device=gpu), torch.tensor(pd_, device=gpu))
+    vals = special_values(lv)
+    nv = len(vals)
+    Qr = 3 * nv
+    pts = lv[rng.integers(0, d, (Qr, 6))]
+    q = lv[rng.integers(0, d, (Qr, 2, 1))]
+    for k, v in enumerate(vals):
+        pts[k, k % 6] = v          # a special point: that entry alone is zero
+        q[nv + k, 0, 0] = v        # a special parent value: the row is zero
+        q[2 * nv + k, 1, 0] = v
+    ref = ob.get_prob(pts, q)
+    got = bf.get_prob(torch.tensor(pts, device=gpu), torch.tensor(q, device=gpu)).cpu().numpy()
+    assert bf.sparse == hashed  # (the CPD is compiled by the first evaluation)
+    assert_factor_close(got, ref)
+    assert (got[ref == 0] == 0).all() and (ref > 0).sum() > 100
+    on = np.array([(lv == v).any() for v in vals])
+    assert (got[nv:][np.tile(~on, 2)] == 0).all() and (got[nv:][np.tile(on, 2)] > 0).any()
+    assert all(got[k, k % 6] == 0 for k in range(nv) if not on[k])
+    # Node.get_prob: evidence on both parents ([Q, 1] columns) and on one (the other free)
+    on_ = OracleNode("E", ["P0", "P1"])
+    on_.fit(nd_, pd_)
+    node = Node("E", "brute_force", {"estimator_name": "brute_force"}, ["P0", "P1"], device=gpu)
+    if hashed:
+        node.estimator.dense_limit = 1
+    node.fit(torch.tensor(nd_, device=gpu), torch.tensor(pd_, device=gpu))
+    e0 = np.concatenate([vals, lv[rng.integers(0, d, nv)]])[:, None].astype(np.float32)
+    e1 = lv[rng.integers(0, d, 2 * nv)][:, None]
+    for qd in ({"P0": e0, "P1": e1}, {"P0": e0}, {"P1": e0}):
+        rp, rd = on_.get_prob(dict(qd), d)
+        gp, gd, _ = node.get_prob({k: torch.tensor(v, device=gpu) for k, v in qd.items()}, d)
+        assert tuple(gp.shape) == rp.shape
+        g = gp.cpu().numpy()
+        assert_factor_close(g, rp)
+        assert (g[rp == 0] == 0).all() and (rp > 0).any()
+        np.testing.assert_array_equal(gd.cpu().numpy(), rd)
+
+
+def test_domain_index_special_values(gpu):
+    """domain_index (device) and domain_index_host on the special list; the
+    expected indices are written out from IEEE ``==``."""
+    dense = np.arange(4, dtype=np.float32)
+    lev = levels(6)  # -0.5 -0.25 0.0 0.25 0.5 0.75
+    # nan -nan inf -inf -0.0 0.0 sub -sub next+ next- below above card -1.0 0.5 2^24+1 2^31 2^32 3e38 -3e38, + two domain values
+    want_dense = [-1, -1, -1, -1, 0, 0, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, 3, 1]
+    want_lev = [-1, -1, -1, -1, 2, 2, -1, -1, -1, -1, -1, -1, -1, -1, 4, -1, -1, -1, -1, -1, 5, 1]
+    for dom, want in ((dense, want_dense), (lev, want_lev)):
+        v = np.concatenate([special_values(dom), dom[[-1, 1]]])
+        assert len(v) == len(want) == 22
+        got = domain_index(torch.tensor(v, device=gpu), torch.tensor(dom, device=gpu))
+        assert got.dtype == torch.int32 and got.cpu().tolist() == want
+        host = domain_index_host(torch.tensor(v), torch.tensor(dom))
+        assert host.dtype == torch.int32 and host.tolist() == want

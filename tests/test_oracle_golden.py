@@ -29,19 +29,23 @@ def _infer_keeping_raw(bn, target, ev, N):
     return pdf, dom, kept["raw"]
 
 
-def _check_golden(name, param, pdf, ref, raw):
+def _check_golden(name, param, pdf, ref, raw, ref_raw=None):
     """The oracle's marginals vs the reference's through the helper, and the
     committed raw max (tests/golden/oracle_raw_max.json) vs the oracle's run."""
     mx, nf, pk = golden_scale(name, param)
     with np.errstate(invalid="ignore"):
         np.testing.assert_array_equal(np.float32(mx), raw.max())  # NaN == NaN here
     if np.isnan(ref).any():
-        # NaN by design (0 / 0: every product of the batch is 0; or the logistic
-        # density's inf / inf).  The reference fixtures hold no unnormalised
-        # rows, so the oracle's own stand on both sides: what this adds to the
-        # NaN positions is the cause -- a batch max of 0, inf or NaN
+        # NaN by design (0 / 0: every product of the batch is 0; the logistic
+        # density's inf / inf; or a NaN / inf evidence value).  The older
+        # reference fixtures hold no unnormalised rows, so the oracle's own
+        # stand on both sides: what this adds to the NaN positions is the cause
+        # -- a batch max of 0, inf or NaN.  The special-evidence fixtures hold
+        # the reference's rows (``ref_raw``): NaN / inf positions equal, the
+        # finite rows at rtol
         assert np.isnan(ref).all() and not (raw.max() > 0 and np.isfinite(raw.max()))
-        assert_marginals_close(pdf, ref, raw_max=mx, n_factors=nf, peak=pk, nan="match", got_raw=raw, ref_raw=raw)
+        assert_marginals_close(pdf, ref, raw_max=mx, n_factors=nf, peak=pk, nan="match", got_raw=raw,
+                               ref_raw=raw if ref_raw is None else ref_raw)
     else:
         assert_marginals_close(pdf, ref, raw_max=mx, n_factors=nf, peak=pk,
                                min_checked_rows=MIN_CHECKED_ROWS.get(name, 0.5))
@@ -67,6 +71,7 @@ def test_oracle_matches_reference_golden(name):
     assert pdf.shape == g["pdf"].shape
     np.testing.assert_array_equal(dom, g["domain"])
     _check_golden(name, False, pdf, g["pdf"], raw)
+    assert (pdf[g["pdf"] == 0] == 0).all()  # what the reference zeroed (an unmatched evidence value) is exactly 0
 
 
 def test_golden_manifest_covers_config0():
@@ -89,7 +94,42 @@ def test_oracle_parametric_matches_reference_golden(name):
     pdf, dom, raw = _infer_keeping_raw(bn, m["target"], ev, m["N_max"])
     assert pdf.shape == g["pdf"].shape
     np.testing.assert_array_equal(dom, g["domain"])
-    _check_golden(name, True, pdf, g["pdf"], raw)
+    _check_golden(name, True, pdf, g["pdf"], raw, g.get("raw"))
+    if "raw" in g:  # the case is exercised: NaN rows beside finite, nonzero ones
+        assert np.isnan(g["raw"][5]).all() and (np.isfinite(g["raw"]).all(1) & (g["raw"] > 0).any(1)).sum() >= 16
+
+
+ACTIVATIONS = ["relu", "tanh", "sigmoid", "leakyrelu", "gelu", "elu"]
+
+
+@pytest.mark.parametrize("act", ACTIVATIONS)
+def test_oracle_activation_matches_reference_on_special_values(act):
+    """``_act`` vs the reference's own torch modules (tests/golden/
+    make_golden_activation.py) at NaN of both signs, +-inf, +-0, subnormals,
+    +-2^-126, 0.625 and its float neighbours, 88.7, 104, 1e30, FLT_MAX: NaN
+    positions, inf positions and zeros WITH their sign exactly; every other
+    value at this file's rtol 1e-5 plus one subnormal step (a single value,
+    parity.assert_factor_close)."""
+    import os
+
+    from oracle.ref_infer import _act
+    from parity import assert_factor_close
+
+    z = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "activation_special.npz"))
+    x, ref = z["x"], z["y_" + act]
+    assert x.size == 24 and np.isnan(x[:2]).all() and np.signbit(x[1]) and np.isinf(x[-2:]).all()
+    assert sorted(k[2:] for k in z.files if k.startswith("y_")) == sorted(ACTIVATIONS)
+    with np.errstate(all="ignore"):
+        got = _act(act, x.copy())
+    assert got.dtype == np.float32
+    for name, f in (("NaN", np.isnan), ("+inf", np.isposinf), ("-inf", np.isneginf), ("zero", lambda a: a == 0)):
+        assert np.array_equal(f(got), f(ref)), f"{act}: {name} positions differ at x = {x[f(got) != f(ref)]}"
+    zero = ref == 0
+    assert np.array_equal(np.signbit(got[zero]), np.signbit(ref[zero])), \
+        f"{act}: signs of zero differ at x = {x[zero][np.signbit(got[zero]) != np.signbit(ref[zero])]}"
+    fin = np.isfinite(ref) & ~zero
+    assert fin.sum() >= 8
+    assert_factor_close(got[fin], ref[fin])
 
 
 def _full(name):
