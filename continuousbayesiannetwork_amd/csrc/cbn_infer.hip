@@ -168,6 +168,27 @@ __device__ __forceinline__ unsigned wave_max_u(unsigned v) {
     return v;
 }
 
+// The same max (wave-uniform) without LDS round trips, for the grid barrier's
+// exit, where it sits on every block's critical path: four DPP steps reduce
+// each row of 16 lanes (quad swaps, then the row's half and full mirror), four
+// v_readlane fetch the rows' maxima.  All 64 lanes must be active.
+__device__ __forceinline__ unsigned wave_max_u_dpp(unsigned v) {
+    auto step = [&](auto ctrl) {
+        v = max(v, (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, decltype(ctrl)::value, 0xf, 0xf, false));
+    };
+    step(std::integral_constant<int, 0xB1>{});   // quad_perm [1, 0, 3, 2]
+    step(std::integral_constant<int, 0x4E>{});   // quad_perm [2, 3, 0, 1]
+    step(std::integral_constant<int, 0x141>{});  // row_half_mirror
+    step(std::integral_constant<int, 0x140>{});  // row_mirror
+    const unsigned a = __builtin_amdgcn_readlane((int)v, 0), b = __builtin_amdgcn_readlane((int)v, 16);
+    const unsigned c = __builtin_amdgcn_readlane((int)v, 32), d = __builtin_amdgcn_readlane((int)v, 48);
+    return max(max(a, b), max(c, d));
+}
+
+// wave_max for values that are >= +0 and not NaN (products of probabilities and
+// their maxima): there the unsigned order of the bit patterns is the float order.
+__device__ __forceinline__ float wave_max_nonneg(float v) { return __uint_as_float(wave_max_u_dpp(__float_as_uint(v))); }
+
 // Diagnostic build only (-DCBN_STAMPS): per-wave s_memtime stamps of the query
 // kernels' phases into a debug buffer (never read by the kernels themselves).
 #ifdef CBN_STAMPS
@@ -651,109 +672,71 @@ constexpr unsigned kSpinLimit = 1u << 22;  // bounded barrier spin (~0.3 s): nev
 // this epoch -- one round trip after the last block arrives instead of a chain
 // of fan-in atomics.  Returns the max word of all blocks.  Bounded spin: a
 // block that never arrives sets sync[2] (the timeout flag) instead of hanging.
-__device__ __forceinline__ unsigned slot_barrier_max(unsigned* __restrict__ sync, unsigned epoch, float bm) {
+//
+// Polling.  Lane i owns slots i, i + 64, ... (KPER of them: 4 covers the 256
+// blocks of a one-block-per-CU grid, kMaxSlots / 64 any grid).  It keeps a
+// pending bit per owned slot: a slot is loaded only while pending (all of a
+// round's loads in flight before any is consumed), its max is folded in once,
+// when the slot first shows this epoch, and the loop ends on a wave-wide
+// ballot of the pending masks.  The 256 blocks poll the same 16 cache lines,
+// and that traffic is what the A/B shows to matter: the later a round, the
+// fewer loads it issues.  Two or three rounds in flight, every slot loaded
+// every round, and other s_sleep spacings were all slower (MEASUREMENTS.md,
+// "the barrier's detection tail").  The final max is taken by DPP: six
+// dependent LDS shuffles there cost every block 0.17 us.
+// Bounded spin: a round takes an agent-scope load round trip plus the s_sleep,
+// >= ~70 ns, so 2^22 rounds bound the wait at ~0.3 s or more, as before.
+template <int KPER>
+__device__ __forceinline__ unsigned slot_poll_max(unsigned* __restrict__ sync, unsigned epoch) {
     const int lane = threadIdx.x & (kWave - 1);
-    unsigned long long* slots = reinterpret_cast<unsigned long long*>(sync + kSlotWordOff);
-    const unsigned long long tag = (unsigned long long)epoch << 32;
-    if (lane == 0)
-        __hip_atomic_store(&slots[blockIdx.x], tag | __float_as_uint(bm), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const unsigned long long* slots = reinterpret_cast<const unsigned long long*>(sync + kSlotWordOff);
     const int G = gridDim.x;
-    constexpr int kPer = kMaxSlots / kWave;
+    unsigned pend = 0;  // bit k: slot lane + 64 k exists and has not shown this epoch yet
+#pragma unroll
+    for (int k = 0; k < KPER; ++k)
+        if (lane + k * kWave < G) pend |= 1u << k;
     unsigned gm = 0;
-    unsigned spins = 0;
-    for (;;) {
-        // all of this round's loads in flight before any is consumed (a
-        // per-slot branch would serialise them: one round trip each)
-        unsigned long long v[kPer];
+    for (unsigned spins = 0; spins <= kSpinLimit; ++spins) {
+        unsigned long long v[KPER] = {};
 #pragma unroll
-        for (int k = 0; k < kPer; ++k)
-            if (k * kWave < G)  // wave-uniform
-                v[k] = __hip_atomic_load(&slots[min(lane + k * kWave, G - 1)], __ATOMIC_RELAXED,
-                                         __HIP_MEMORY_SCOPE_AGENT);
-        bool done = true;
+        for (int k = 0; k < KPER; ++k)
+            if (pend & (1u << k))
+                v[k] = __hip_atomic_load(&slots[lane + k * kWave], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 #pragma unroll
-        for (int k = 0; k < kPer; ++k) {
-            if (k * kWave < G) {
-                const bool here = (v[k] >> 32) == (unsigned long long)epoch;
-                done &= here;
-                const unsigned b = here ? (unsigned)v[k] : 0u;
+        for (int k = 0; k < KPER; ++k) {
+            if ((pend & (1u << k)) && (unsigned)(v[k] >> 32) == epoch) {
+                const unsigned b = (unsigned)v[k];
                 gm = gm > b ? gm : b;
+                pend &= ~(1u << k);
             }
         }
-        if (__builtin_amdgcn_ballot_w64(!done) == 0) break;
+        if (__builtin_amdgcn_ballot_w64(pend != 0) == 0)
+            return wave_max_u_dpp(gm);  // non-negative floats: unsigned order == float order
         __builtin_amdgcn_s_sleep(1);
-        if (++spins > kSpinLimit) {
-            // timed out: flag it on the device (cbn_plan_status) and in the plan's
-            // host-mapped status word (the next cbn_plan_run reports it), and make
-            // this block's rows NaN instead of dividing by a partial max
-            if (lane == 0) {
-                atomicOr(&sync[2], 1u);
-                unsigned* hs = *reinterpret_cast<unsigned* const*>(sync + kHostStatusWordOff);
-                if (hs) __hip_atomic_store(hs, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            }
-            return 0x7fc00000u;  // NaN
-        }
     }
-    return wave_max_u(gm);  // non-negative floats: unsigned order == float order
+    // timed out: flag it on the device (cbn_plan_status) and in the plan's
+    // host-mapped status word (the next cbn_plan_run reports it), and make
+    // this block's rows NaN instead of dividing by a partial max
+    if (lane == 0) {
+        atomicOr(&sync[2], 1u);
+        unsigned* hs = *reinterpret_cast<unsigned* const*>(sync + kHostStatusWordOff);
+        if (hs) __hip_atomic_store(hs, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+    return 0x7fc00000u;  // NaN
 }
 
-#ifdef CBN_BAR2
-// Diagnostic A/B (tools/ab_libs.sh): two-level form of slot_barrier_max.  The
-// blocks of one group (blockIdx % 8: one XCD under the observed round-robin
-// placement -- speed only, the protocol does not depend on it) reduce their
-// 32 slots; each block of the group publishes the same group word {epoch,
-// group max} once it saw all 32 (idempotent stores), and every block then
-// polls the 8 group words: 40 polled words per wave per round instead of 256.
-__device__ __forceinline__ unsigned slot_barrier_max2(unsigned* __restrict__ sync, unsigned epoch, float bm) {
-    const int lane = threadIdx.x & (kWave - 1);
+// Every fused launch has one block per CU at most (fused_capacity,
+// launch_fused_v), 256 on this chip: four slots per lane.  The kMaxSlots form
+// serves a larger co-resident grid (wave-uniform choice, cold code here).
+constexpr int kSlotsPerLaneCu = 4;
+__device__ __forceinline__ unsigned slot_barrier_max(unsigned* __restrict__ sync, unsigned epoch, float bm) {
     unsigned long long* slots = reinterpret_cast<unsigned long long*>(sync + kSlotWordOff);
-    unsigned long long* gslots = slots + kMaxSlots - 8;  // 8 group words: the last slots (fused grid <= #CUs)
-    const unsigned long long tag = (unsigned long long)epoch << 32;
-    if (lane == 0)
-        __hip_atomic_store(&slots[blockIdx.x], tag | __float_as_uint(bm), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const int G = gridDim.x;
-    const int grp = blockIdx.x & 7;
-    unsigned spins = 0;
-    auto timeout = [&]() {
-        if (lane == 0) {
-            atomicOr(&sync[2], 1u);
-            unsigned* hs = *reinterpret_cast<unsigned* const*>(sync + kHostStatusWordOff);
-            if (hs) __hip_atomic_store(hs, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        }
-    };
-    // level 1: this group's slots grp, grp + 8, ... (< G); lane i owns slot grp + 8 i
-    unsigned gm = 0;
-    for (;;) {
-        const int s = grp + 8 * lane;
-        unsigned long long v = s < G ? __hip_atomic_load(&slots[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : tag;
-        const bool here = (v >> 32) == (unsigned long long)epoch;
-        if (__builtin_amdgcn_ballot_w64(!here) == 0) {
-            gm = wave_max_u(s < G ? (unsigned)v : 0u);
-            break;
-        }
-        __builtin_amdgcn_s_sleep(1);
-        if (++spins > kSpinLimit) {
-            timeout();
-            return 0x7fc00000u;
-        }
-    }
-    if (lane == 0)
-        __hip_atomic_store(&gslots[grp], tag | gm, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    // level 2: the 8 group words (groups with no block: G < 8)
-    for (;;) {
-        unsigned long long v = (lane < 8 && lane < G) ? __hip_atomic_load(&gslots[lane], __ATOMIC_RELAXED,
-                                                                          __HIP_MEMORY_SCOPE_AGENT) : tag;
-        const bool here = (v >> 32) == (unsigned long long)epoch;
-        if (__builtin_amdgcn_ballot_w64(!here) == 0) return wave_max_u((lane < 8 && lane < G) ? (unsigned)v : 0u);
-        __builtin_amdgcn_s_sleep(1);
-        if (++spins > kSpinLimit) {
-            timeout();
-            return 0x7fc00000u;
-        }
-    }
+    if ((threadIdx.x & (kWave - 1)) == 0)
+        __hip_atomic_store(&slots[blockIdx.x], ((unsigned long long)epoch << 32) | __float_as_uint(bm),
+                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (gridDim.x <= kSlotsPerLaneCu * kWave) return slot_poll_max<kSlotsPerLaneCu>(sync, epoch);
+    return slot_poll_max<kMaxSlots / kWave>(sync, epoch);
 }
-#define slot_barrier_max slot_barrier_max2
-#endif
 
 template <int VPL, bool USE_LDS, int MODE, int NP>
 __global__ void __launch_bounds__(kQueryThreads)
@@ -2232,15 +2215,21 @@ k_query_staged(const float* __restrict__ gimage, int image_floats, int rec_off, 
             for (int i = (int)gridDim.x + tid; i < n_max; i += kQueryThreads) max_out[i] = 0u;
     }
     if (MODE == kModeFused) {
-        lmax = wave_max(lmax);
+        // The two reductions in front of the publish by DPP: no LDS round trips
+        // on the way into the barrier.  wave_max_nonneg orders floats by their
+        // bit patterns, which needs lmax >= +0 and not NaN: it starts at +0 and
+        // only takes fmaxf with products of table entries, which are >= +0 (so
+        // never -0), and fmaxf drops a NaN operand.
+        lmax = wave_max_nonneg(lmax);
         if (lane == 0) wmax[wid] = lmax;
         __syncthreads();
         CBN_STAMP(7);
         if (wid == 0) {
+            const float bm = wave_max_nonneg(lane < kQueryThreads / kWave ? wmax[lane] : 0.f);
 #ifdef CBN_ABL_NOBAR
-            const unsigned gm = __float_as_uint(wave_max(lane < kQueryThreads / kWave ? wmax[lane] : 0.f));
+            const unsigned gm = __float_as_uint(bm);
 #else
-            const unsigned gm = slot_barrier_max(sync, epoch, wave_max(lane < kQueryThreads / kWave ? wmax[lane] : 0.f));
+            const unsigned gm = slot_barrier_max(sync, epoch, bm);
 #endif
             if (lane == 0) {
                 wmax[0] = __uint_as_float(gm);

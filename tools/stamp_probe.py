@@ -66,6 +66,10 @@ t0 = e.min()
 print("block entry (ticks after first): p50 %d p90 %d max %d" % tuple(np.percentile(e - t0, [50, 90, 100])))
 print("block arrival at barrier:        p50 %d p90 %d max %d" % tuple(np.percentile(a - t0, [50, 90, 100])))
 print("per-block entry->arrival:        p50 %d p90 %d max %d" % tuple(np.percentile(a - e, [50, 90, 100])))
+if bn.engine.fused:  # the grid barrier (polled by wave 0) and the block's hand-off behind it
+    for name, d in (("7 -> 8  barrier entry -> release, wave 0", full[:nb, 0, 8] - full[:nb, 0, 7]),
+                    ("8 -> 10 wave 0's release -> rows stored, all waves", full[:nb, :, 10] - full[:nb, :1, 8])):
+        print("%-52s p10 %d p50 %d p90 %d max %d" % ((name + ":",) + tuple(np.percentile(d, [10, 50, 90, 100]))))
 late = np.argsort(e)[-8:]
 print("latest-entering blocks:", late.tolist(), (e[late] - t0).tolist())
 grp = np.array([e[b::8].min() - t0 for b in range(8)])
