@@ -172,3 +172,32 @@ class BayesianNetwork:
             pred[n:n + batch_size] = torch.gather(domain, dim=1, index=idx).squeeze(1).cpu().numpy()
             bar.update(min(n + batch_size, len(data)) - n)
         return pred
+
+    def predict(self, target_node: str, evidence: Dict[str, torch.Tensor] = None, N_max: int = 16,
+                return_index: bool = False):
+        """The target's most probable sample point per evidence row: what
+        ``benchmarking_df`` (bayesian_network.py:329-373) takes from every
+        ``infer`` result -- ``argmax`` over each row, the domain value there --
+        in one launch that stores no [n_queries, N_max] pdf
+        (``InferenceEngine.predict``; first maximum of the unnormalised row,
+        ties to the lowest index).
+
+        :param evidence: {node: tensor [n_queries, 1]}, as ``infer``
+        :return: value [n_queries], or (value, index int32 [n_queries])
+        """
+        index, value, _ = self.engine.predict(target_node, evidence, N_max)
+        return (value, index) if return_index else value
+
+    def predict_df(self, data: pd.DataFrame, target_feature: str, batch_size: int = 128, N_max: int = 16) -> np.ndarray:
+        """``benchmarking_df``'s interface and return type on ``predict``: the
+        batches' predictions stay on the device and come back in one copy."""
+        feats = [f for f in data.columns if f != target_feature]
+        # float32 on the device once (the conversion infer applies to every batch)
+        values = {f: torch.tensor(data[f].values).unsqueeze(-1).to(device=self.device, dtype=torch.float32)
+                  for f in feats}
+        out = []
+        for n in range(0, len(data), batch_size):  # (the last batch may be short)
+            out.append(self.predict(target_feature, {f: values[f][n:n + batch_size] for f in feats}, N_max=N_max))
+        if not out:
+            return np.zeros((0,))
+        return torch.cat(out).cpu().numpy().astype(np.float64)

@@ -189,6 +189,90 @@ __device__ __forceinline__ unsigned wave_max_u_dpp(unsigned v) {
 // their maxima): there the unsigned order of the bit patterns is the float order.
 __device__ __forceinline__ float wave_max_nonneg(float v) { return __uint_as_float(wave_max_u_dpp(__float_as_uint(v))); }
 
+// ---- arg-max epilogue (kModeArgmax launches, k_row_argmax) -----------------
+// Where a prediction's three outputs go: per query, the first index of the row
+// maximum, the target's sample point at that index (tv[index]; skipped when tv
+// or value is null) and the row maximum itself (skipped when null).
+struct ArgmaxOut {
+    const float* tv;
+    int* index;
+    float* value;
+    float* row_max;
+};
+
+// One (value, column) candidate as a 64-bit unsigned key whose order is
+// "larger value first, then lower column": (order word << 32) | (~0u - column).
+// `ord` must order like the values compared: for the table kernels' products --
+// finite, >= +0, never NaN or -0, the invariant wave_max_nonneg relies on -- the
+// float's own bit pattern does (argmax_store); k_row_argmax maps any float
+// first (amax_ord).
+__device__ __forceinline__ unsigned long long amax_key_u(unsigned ord, int col) {
+    return ((unsigned long long)ord << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned)col);
+}
+__device__ __forceinline__ int amax_col(unsigned long long k) { return (int)(0xFFFFFFFFu - (unsigned)k); }
+__device__ __forceinline__ unsigned long long umax64(unsigned long long a, unsigned long long b) { return a > b ? a : b; }
+
+template <int CTRL>
+__device__ __forceinline__ unsigned long long dpp_u64(unsigned long long k) {
+    const unsigned lo = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)k, CTRL, 0xf, 0xf, false);
+    const unsigned hi = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)(k >> 32), CTRL, 0xf, 0xf, false);
+    return ((unsigned long long)hi << 32) | lo;
+}
+
+// Max of the keys of one query's L lanes: lane `l` of the L consecutive lanes
+// [lane - l, lane - l + L) of ONE wave (the fast path's plan gate keeps 64 a
+// multiple of L, so a query never straddles waves).  Valid for any
+// 1 <= L <= 64; the result is in the query's lane l == 0 (L = 2, 4: in every
+// lane).  L = 2 and 4 are aligned pairs / quads: one / two quad_perm DPP steps,
+// no LDS round trip.  Every lane of the wave must be active.
+__device__ __forceinline__ unsigned long long seg_max_key(unsigned long long k, int l, int L) {
+    if (L == 1) return k;
+    if (L == 2) return umax64(k, dpp_u64<0xB1>(k));  // quad_perm [1, 0, 3, 2]
+    if (L == 4) {
+        k = umax64(k, dpp_u64<0xB1>(k));
+        return umax64(k, dpp_u64<0x4E>(k));  // quad_perm [2, 3, 0, 1]
+    }
+    // after the step of offset o, lane l holds the max over lanes [l, l + 2o) of its query
+    for (int o = 1; o < L; o <<= 1) {
+        const unsigned long long t = __shfl_down(k, o, kWave);
+        if (l + o < L) k = umax64(k, t);
+    }
+    return k;
+}
+
+// The arg-max launch's epilogue: acc[4 v + i] is the product of column
+// colv[v] + i of query q.  Each lane reduces its columns to one key (by COLUMN
+// NUMBER: the paired layouts permute colv), the query's L lanes reduce theirs,
+// and lane l == 0 stores.  Called by every lane of the wave (`valid`: the lane
+// holds a query of the batch).
+template <int NB>
+__device__ __forceinline__ void argmax_store(const float (&acc)[4 * NB], const int (&colv)[NB], int l, int L, bool valid,
+                                             long long q, const ArgmaxOut& am) {
+    unsigned long long k = 0;
+#pragma unroll
+    for (int v = 0; v < NB; ++v) {
+        // within a block the columns ascend with i: a strict 32-bit compare keeps the lowest
+        unsigned b = __float_as_uint(acc[4 * v]);
+        int c = colv[v];
+#pragma unroll
+        for (int i = 1; i < 4; ++i) {
+            const unsigned bi = __float_as_uint(acc[4 * v + i]);
+            if (bi > b) {
+                b = bi;
+                c = colv[v] + i;
+            }
+        }
+        k = umax64(k, amax_key_u(b, c));
+    }
+    k = seg_max_key(k, l, L);
+    if (valid && l == 0) {
+        const int idx = amax_col(k);
+        am.index[q] = idx;
+        if (am.value && am.tv) am.value[q] = am.tv[idx];
+        if (am.row_max) am.row_max[q] = __uint_as_float((unsigned)(k >> 32));
+    }
+}
+
 // Diagnostic build only (-DCBN_STAMPS): per-wave s_memtime stamps of the query
 // kernels' phases into a debug buffer (never read by the kernels themselves).
 #ifdef CBN_STAMPS
@@ -661,7 +745,11 @@ constexpr int kLoc = 8;
 // products and publishes this launch's max like MODE 0 (the sharded path
 // all-reduces that max across ranks, then k_scale divides in place: the same
 // fp32 division acc / max as the single-launch path, so the rows are identical).
-constexpr int kModeMax = 0, kModeWrite = 1, kModeFused = 2, kModeRaw = 3;
+// MODE 4 (arg-max): launched like the raw mode -- same grid, same rounds, same
+// products in the same order, no grid barrier -- but instead of the row it
+// stores each query's (index, value, row_max) (argmax_store) and publishes no
+// max words: a prediction needs neither the batch max nor the division.
+constexpr int kModeMax = 0, kModeWrite = 1, kModeFused = 2, kModeRaw = 3, kModeArgmax = 4;
 constexpr unsigned kSpinLimit = 1u << 22;  // bounded barrier spin (~0.3 s): never hang
 
 // Fused grid barrier on the global max, called by ONE wave per block (all
@@ -743,7 +831,7 @@ __global__ void __launch_bounds__(kQueryThreads)
 k_query_fast(int rec_off, int nf, int ns, const float* __restrict__ gimage, int image_floats, FPtrsT<NP> fp,
              long long Q, long long per, int N, int RS, int L, int paired, unsigned* __restrict__ sync,
              unsigned epoch, const unsigned* __restrict__ max_in, int n_max, unsigned* __restrict__ max_out,
-             float* __restrict__ out, int lds_tab, unsigned long long lmask0, unsigned long long lmask1) {
+             float* __restrict__ out, int lds_tab, unsigned long long lmask0, unsigned long long lmask1, ArgmaxOut am) {
     CBN_STAMP_INIT;
     extern __shared__ __attribute__((aligned(16))) float4 smem4[];
     float* simg = reinterpret_cast<float*>(smem4);
@@ -1012,6 +1100,7 @@ k_query_fast(int rec_off, int nf, int ns, const float* __restrict__ gimage, int 
             }
         }
         if (first) CBN_STAMP(5);
+        if (MODE == kModeArgmax) argmax_store<VPL>(acc, col, l, L, valid, q, am);  // (wave-uniform call site)
         if (valid && CBN_OK_OR(q < Q && (long long)(l + 1) * VPL * 4 <= N, 3)) {
             if (MODE == kModeFused) fq = q;
             if (MODE == kModeWrite) {
@@ -1028,7 +1117,7 @@ k_query_fast(int rec_off, int nf, int ns, const float* __restrict__ gimage, int 
                         make_float4(acc[4 * v], acc[4 * v + 1], acc[4 * v + 2], acc[4 * v + 3]);
 #pragma unroll
                 for (int i = 0; i < NV; ++i) lmax = fmaxf(lmax, acc[i]);
-            } else {
+            } else if (MODE != kModeArgmax) {
 #pragma unroll
                 for (int i = 0; i < NV; ++i) lmax = fmaxf(lmax, acc[i]);
             }
@@ -1131,7 +1220,8 @@ __global__ void __launch_bounds__(kQueryThreads)
 k_query_cols(int rec_off, int nf, int ns, const float* __restrict__ gimage, int image_floats,
              FPtrsT<kFastPtrsSmall> sp, long long Q, long long per, int N, int RS, int L,
              unsigned* __restrict__ sync, unsigned epoch, const unsigned* __restrict__ max_in, int n_max,
-             unsigned* __restrict__ max_out, float* __restrict__ out, int lds_tab, const int* __restrict__ crec) {
+             unsigned* __restrict__ max_out, float* __restrict__ out, int lds_tab, const int* __restrict__ crec,
+             ArgmaxOut am) {
     CBN_STAMP_INIT;
     extern __shared__ __attribute__((aligned(16))) float4 smem4[];
     float* simg = reinterpret_cast<float*>(smem4);
@@ -1309,6 +1399,7 @@ k_query_cols(int rec_off, int nf, int ns, const float* __restrict__ gimage, int 
 #pragma unroll
             for (int i = 0; i < NV; ++i) acc0[i] = acc[i];
         }
+        if (MODE == kModeArgmax) argmax_store<VPL>(acc, col, l, L, valid, q, am);  // (wave-uniform call site)
         if (valid) {
             if (MODE == kModeFused && !first) fq = q;
             if (MODE == kModeWrite) {
@@ -1325,7 +1416,7 @@ k_query_cols(int rec_off, int nf, int ns, const float* __restrict__ gimage, int 
                         make_float4(acc[4 * v], acc[4 * v + 1], acc[4 * v + 2], acc[4 * v + 3]);
 #pragma unroll
                 for (int i = 0; i < NV; ++i) lmax = fmaxf(lmax, acc[i]);
-            } else {
+            } else if (MODE != kModeArgmax) {
 #pragma unroll
                 for (int i = 0; i < NV; ++i) lmax = fmaxf(lmax, acc[i]);
             }
@@ -1427,7 +1518,8 @@ __global__ void __launch_bounds__(kQueryThreads)
 k_query_slots(int nf, int ns, const float* __restrict__ gimage, int qslot_off, const int* __restrict__ crec,
               FPtrsT<kFastPtrsSmall> sp, long long Q, long long per, int N, int L, unsigned* __restrict__ sync,
               unsigned epoch, const unsigned* __restrict__ max_in, int n_max, unsigned* __restrict__ max_out,
-              float* __restrict__ out, int lds_tab, unsigned long long lmask0, unsigned long long lmask1, int coal) {
+              float* __restrict__ out, int lds_tab, unsigned long long lmask0, unsigned long long lmask1, int coal,
+              ArgmaxOut am) {
     CBN_STAMP_INIT;
     extern __shared__ __attribute__((aligned(16))) float4 smem4[];
     float* simg = reinterpret_cast<float*>(smem4);
@@ -1739,6 +1831,7 @@ k_query_slots(int nf, int ns, const float* __restrict__ gimage, int qslot_off, c
 #pragma unroll
             for (int i = 0; i < NV; ++i) acc0[i] = acc[i];
         }
+        if (MODE == kModeArgmax) argmax_store<VPL>(acc, col, l, L, valid, q, am);  // (wave-uniform call site)
         if (valid) {
             if (MODE == kModeFused && !first) fq = q;
             if (MODE == kModeWrite) {
@@ -1755,7 +1848,7 @@ k_query_slots(int nf, int ns, const float* __restrict__ gimage, int qslot_off, c
                         make_float4(acc[4 * v], acc[4 * v + 1], acc[4 * v + 2], acc[4 * v + 3]);
 #pragma unroll
                 for (int i = 0; i < NV; ++i) lmax = fmaxf(lmax, acc[i]);
-            } else {
+            } else if (MODE != kModeArgmax) {
 #pragma unroll
                 for (int i = 0; i < NV; ++i) lmax = fmaxf(lmax, acc[i]);
             }
@@ -1874,7 +1967,7 @@ __global__ void __launch_bounds__(kQueryThreads)
 k_query_staged(const float* __restrict__ gimage, int image_floats, int rec_off, int nf, int zero_off, long long Q,
                long long per, unsigned* __restrict__ sync, unsigned epoch, const unsigned* __restrict__ max_in,
                int n_max, unsigned* __restrict__ max_out, float* __restrict__ out, FoldJob fold,
-               FPtrsT<kFastPtrsSmall> fp) {
+               FPtrsT<kFastPtrsSmall> fp, ArgmaxOut am) {
     CBN_STAMP_INIT;
     constexpr int N = 32;
     extern __shared__ __attribute__((aligned(16))) float4 smem4[];
@@ -2152,6 +2245,12 @@ k_query_staged(const float* __restrict__ gimage, int image_floats, int rec_off, 
         }
 #endif
         CBN_STAMP(5);
+        if (MODE == kModeArgmax) {
+            // an aligned quad holds the row; for odd query slots clo > chi, so the
+            // keys carry the column numbers, not the register positions
+            const int colv[2] = {clo, chi};
+            argmax_store<2>(acc, colv, l, 4, q < q1, q, am);
+        }
         if (q < q1) {
             if (MODE == kModeFused) fq = q;
             if (MODE == kModeRaw && wt_raw) {
@@ -2169,7 +2268,7 @@ k_query_staged(const float* __restrict__ gimage, int image_floats, int rec_off, 
                     ? make_float4(acc[4] / dv, acc[5] / dv, acc[6] / dv, acc[7] / dv)
                     : make_float4(acc[4], acc[5], acc[6], acc[7]);
             }
-            if (MODE != kModeWrite)
+            if (MODE != kModeWrite && MODE != kModeArgmax)
 #pragma unroll
                 for (int i = 0; i < 8; ++i) lmax = fmaxf(lmax, acc[i]);
         }
@@ -2361,9 +2460,76 @@ __global__ void __launch_bounds__(64) k_reduce_max(const unsigned* __restrict__ 
     if (threadIdx.x == 0) *out = m;
 }
 
+// Order word of ANY float for amax_key_u, with torch.argmax's rules: a NaN is
+// greater than every number (all NaNs equal, so the first one wins), -0 == +0,
+// otherwise the float order (sign-magnitude bits -> a monotone unsigned).
+__device__ __forceinline__ unsigned amax_ord(float v) {
+    if (v != v) return 0xFFFFFFFFu;
+    const unsigned b = __float_as_uint(v + 0.f);  // -0 + +0 = +0
+    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+
+// (index, value, row_max) of stored rows [n_rows, n_cols]: the prediction of
+// every plan without an arg-max epilogue in its query kernel (generic, direct,
+// wide-column and parametric plans; their rows can hold NaN and inf, hence the
+// full comparison rules of amax_ord).  VEC: the row is split over LR lanes (a
+// power of two <= 64, >= n_cols / 4 when that is <= 64) reading coalesced 16-B
+// pieces, 64 / LR rows per wave; else one lane walks one row.  row_max is
+// re-read at the winning column, so it is the stored value bit for bit.
+constexpr int kRowThreads = 256;
+template <bool VEC>
+__global__ void __launch_bounds__(kRowThreads)
+k_row_argmax(const float* __restrict__ rows, long long n_rows, int n_cols, int LR, ArgmaxOut am) {
+    const int l = VEC ? (int)(threadIdx.x & (unsigned)(LR - 1)) : 0;
+    const long long rpb = kRowThreads / LR;  // rows per block pass
+    // (block-uniform trip count: every lane stays active for the DPP steps)
+    for (long long r0 = (long long)blockIdx.x * rpb; r0 < n_rows; r0 += (long long)gridDim.x * rpb) {
+        const long long rr = r0 + threadIdx.x / LR;
+        const bool valid = rr < n_rows;
+        const long long r = valid ? rr : n_rows - 1;
+        const float* row = rows + r * n_cols;
+        unsigned long long k = 0;
+        if (VEC) {
+            const float4* row4 = reinterpret_cast<const float4*>(row);
+            for (int c4 = l; c4 < n_cols / 4; c4 += LR) {
+                const float4 t = row4[c4];
+                k = umax64(k, amax_key_u(amax_ord(t.x), 4 * c4));
+                k = umax64(k, amax_key_u(amax_ord(t.y), 4 * c4 + 1));
+                k = umax64(k, amax_key_u(amax_ord(t.z), 4 * c4 + 2));
+                k = umax64(k, amax_key_u(amax_ord(t.w), 4 * c4 + 3));
+            }
+            k = seg_max_key(k, l, LR);
+        } else {
+            for (int c = 0; c < n_cols; ++c) k = umax64(k, amax_key_u(amax_ord(row[c]), c));
+        }
+        if (valid && l == 0) {
+            const int idx = amax_col(k);
+            am.index[r] = idx;
+            if (am.value && am.tv) am.value[r] = am.tv[idx];
+            if (am.row_max) am.row_max[r] = row[idx];
+        }
+    }
+}
+
 int g_num_cu = 0;
 
 }  // namespace
+
+// index / value / row_max of rows [n_rows, n_cols] on `s` (k_row_argmax)
+static int launch_row_argmax(const float* rows, long long n_rows, int n_cols, const ArgmaxOut& am, hipStream_t s) {
+    const bool vec = n_cols % 4 == 0 && reinterpret_cast<uintptr_t>(rows) % 16 == 0;
+    int LR = 1;
+    if (vec)
+        while (LR < n_cols / 4 && LR < kWave) LR <<= 1;
+    const long long rpb = kRowThreads / LR;
+    const long long blocks = std::max(1LL, std::min((n_rows + rpb - 1) / rpb, (long long)num_cu() * 16));
+    if (vec)
+        hipLaunchKernelGGL(k_row_argmax<true>, dim3((unsigned)blocks), dim3(kRowThreads), 0, s, rows, n_rows, n_cols, LR, am);
+    else
+        hipLaunchKernelGGL(k_row_argmax<false>, dim3((unsigned)blocks), dim3(kRowThreads), 0, s, rows, n_rows, n_cols, LR, am);
+    HIP_TRY(hipGetLastError());
+    return CBN_OK;
+}
 
 int cbn::num_cu() {
     if (g_num_cu == 0) {
@@ -2434,17 +2600,19 @@ size_t slots_lds_bytes(long long lds_tab_floats, int ns, int nf, int QB) {
 // one fast-kernel launch with the pointer table sized to the plan
 template <int VPL, bool LDS, int MODE, int NP>
 void launch_fast_np(const cbn_plan* p, unsigned blocks, hipStream_t s, const EvPtrs& ev, long long Q, int L,
-                    unsigned epoch, const unsigned* max_in, int n_max, unsigned* max_out, float* out) {
+                    unsigned epoch, const unsigned* max_in, int n_max, unsigned* max_out, float* out,
+                    const ArgmaxOut& am) {
     hipLaunchKernelGGL((k_query_fast<VPL, LDS, MODE, NP>), dim3(blocks), dim3(kQueryThreads), p->fast_lds_bytes, s,
                        p->rec_off, p->nf, p->ns, p->d_image, p->image_floats, fast_ptrs<NP>(p, ev), Q,
                        (Q + blocks - 1) / blocks, p->N, p->RS, L, p->paired ? 1 : 0, p->d_sync, epoch, max_in, n_max,
-                       max_out, out, p->lds_tab_floats, p->lds_tab_mask[0], p->lds_tab_mask[1]);
+                       max_out, out, p->lds_tab_floats, p->lds_tab_mask[0], p->lds_tab_mask[1], am);
 }
 
 template <int VPL, bool LDS, int MODE>
 void launch_fast_k(const cbn_plan* p, unsigned blocks, hipStream_t s, const EvPtrs& ev, long long Q, int L,
                    unsigned epoch, const unsigned* max_in, int n_max, unsigned* max_out, float* out,
-                   const FoldJob* fold = nullptr) {
+                   const FoldJob* fold = nullptr, const ArgmaxOut* amp = nullptr) {
+    const ArgmaxOut am = amp ? *amp : ArgmaxOut{nullptr, nullptr, nullptr, nullptr};  // (read by kModeArgmax only)
     if (p->staged) {  // paired N = 32 layout in LDS: the staged kernel (same grid, same words)
         FoldJob fj;
         memset(&fj, 0, sizeof(fj));
@@ -2456,7 +2624,7 @@ void launch_fast_k(const cbn_plan* p, unsigned blocks, hipStream_t s, const EvPt
         hipLaunchKernelGGL((k_query_staged<MODE>), dim3(blocks), dim3(kQueryThreads), p->staged_lds_bytes, s,
                            p->d_image, p->image_floats, p->rec_off + p->prefix * kRecFloats, p->nf - p->prefix,
                            p->zero_off, Q, (Q + blocks - 1) / blocks, p->d_sync, epoch, max_in, n_max, max_out, out,
-                           fj, fast_ptrs<kFastPtrsSmall>(p, ev, p->prefix));
+                           fj, fast_ptrs<kFastPtrsSmall>(p, ev, p->prefix), am);
         return;
     }
     if (p->slots) {
@@ -2477,7 +2645,7 @@ void launch_fast_k(const cbn_plan* p, unsigned blocks, hipStream_t s, const EvPt
         hipLaunchKernelGGL((k_query_slots<VPL, MODE>), dim3(blocks), dim3(kQueryThreads), p->fast_lds_bytes, s, p->nf,
                            p->ns, p->d_image, p->rec_off + p->nf * kRecFloats, p->d_crec, slot_ptrs(p, ev), Q, per,
                            p->N, L, p->d_sync, epoch, max_in, n_max, max_out, out, p->lds_tab_floats,
-                           p->lds_tab_mask[0], p->lds_tab_mask[1], coal);
+                           p->lds_tab_mask[0], p->lds_tab_mask[1], coal, am);
         return;
     }
     if (p->cols) {
@@ -2485,13 +2653,13 @@ void launch_fast_k(const cbn_plan* p, unsigned blocks, hipStream_t s, const EvPt
         hipLaunchKernelGGL(k, dim3(blocks), dim3(kQueryThreads), p->fast_lds_bytes, s,
                            p->rec_off, p->nf, p->ns, p->d_image, p->image_floats, slot_ptrs(p, ev), Q,
                            (Q + blocks - 1) / blocks, p->N, p->RS, L, p->d_sync, epoch, max_in, n_max, max_out, out,
-                           p->lds_tab_floats, p->d_crec);
+                           p->lds_tab_floats, p->d_crec, am);
         return;
     }
     if (p->nf * kFastObs <= kFastPtrsSmall)
-        launch_fast_np<VPL, LDS, MODE, kFastPtrsSmall>(p, blocks, s, ev, Q, L, epoch, max_in, n_max, max_out, out);
+        launch_fast_np<VPL, LDS, MODE, kFastPtrsSmall>(p, blocks, s, ev, Q, L, epoch, max_in, n_max, max_out, out, am);
     else
-        launch_fast_np<VPL, LDS, MODE, kFastPtrs>(p, blocks, s, ev, Q, L, epoch, max_in, n_max, max_out, out);
+        launch_fast_np<VPL, LDS, MODE, kFastPtrs>(p, blocks, s, ev, Q, L, epoch, max_in, n_max, max_out, out, am);
 }
 
 template <int VPL, bool LDS, int MODE>
@@ -2575,6 +2743,18 @@ int launch_raw_v(cbn_plan* p, long long Q, const EvPtrs& ev, unsigned* max_bits,
     return CBN_OK;
 }
 
+// The arg-max launch: the raw launch's grid and rounds, no rows, no max words.
+template <int VPL, bool LDS>
+int launch_argmax_v(cbn_plan* p, long long Q, const EvPtrs& ev, const ArgmaxOut& am, hipStream_t s) {
+    const int L = p->N / (4 * VPL);
+    const long long cap = std::max(1, p->max_slots - raw_reserve_cu());
+    long long blocks = (Q * L + kQueryThreads - 1) / kQueryThreads;
+    if (blocks > cap) blocks = cap;
+    launch_fast_k<VPL, LDS, kModeArgmax>(p, (unsigned)blocks, s, ev, Q, L, 0u, nullptr, 0, nullptr, nullptr, nullptr, &am);
+    HIP_TRY(hipGetLastError());
+    return CBN_OK;
+}
+
 // public pass API on the fast kernel: max pass -> per-block words -> one word
 template <int VEC, bool LDS, bool WRITE>
 int launch_fast(cbn_plan* p, long long Q, const EvPtrs& ev, unsigned* max_bits, float* out, hipStream_t s) {
@@ -2639,8 +2819,13 @@ void allow_lds(size_t bytes) {
         allow_fast_lds<2, LDS, kModeFused>((int)bytes);
         allow_fast_lds<1, LDS, kModeRaw>((int)bytes);
         allow_fast_lds<2, LDS, kModeRaw>((int)bytes);
+        allow_fast_lds<1, LDS, kModeArgmax>((int)bytes);
+        allow_fast_lds<2, LDS, kModeArgmax>((int)bytes);
     }
 }
+
+// the plan's arg-max runs in its query kernel (kModeArgmax): every fast-path table plan
+bool argmax_native(const cbn_plan* p) { return p->fast && !p->param && !p->direct; }
 
 long long fused_capacity(const cbn_plan* p) {
     if (!p->fast || !p->fused_ok) return 0;
@@ -3014,6 +3199,10 @@ int cbn_plan_create(const cbn_factor_desc* factors, int32_t n_factors, int32_t n
         ok = hipMemcpy(P->d_image + zero_off + 64, ones.data(), sizeof(float) * 64, hipMemcpyHostToDevice) == hipSuccess;
     }
     ok = ok && hipMemset(P->d_sync, 0, sizeof(unsigned) * kSyncWords) == hipSuccess;
+    if (ok) {  // the bits of 1.0f: the max word of cbn_plan_run_argmax's generic-plan rows (x / 1.0f = x)
+        const float one = 1.f;
+        ok = hipMemcpy(P->d_sync + kOneWordOff, &one, sizeof(one), hipMemcpyHostToDevice) == hipSuccess;
+    }
     // host-mapped status word of the fused launches' timeout (polled for free by cbn_plan_run);
     // its device address lives in the sync buffer for the (rare) timeout path
     ok = ok && hipHostMalloc(reinterpret_cast<void**>(&P->h_status), sizeof(unsigned),
@@ -3088,7 +3277,8 @@ int cbn_plan_create(const cbn_factor_desc* factors, int32_t n_factors, int32_t n
                 for (const void* fn : {reinterpret_cast<const void*>(&k_query_staged<kModeMax>),
                                        reinterpret_cast<const void*>(&k_query_staged<kModeWrite>),
                                        reinterpret_cast<const void*>(&k_query_staged<kModeFused>),
-                                       reinterpret_cast<const void*>(&k_query_staged<kModeRaw>)})
+                                       reinterpret_cast<const void*>(&k_query_staged<kModeRaw>),
+                                       reinterpret_cast<const void*>(&k_query_staged<kModeArgmax>)})
                     (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBudget);
             }
             P->fast_lds_bytes =
@@ -3498,6 +3688,73 @@ int cbn_plan_run_fold(cbn_plan* plan, int64_t n_queries, const float* const* evi
     return CBN_OK;
 }
 
+int cbn_row_argmax(const float* rows, int64_t n_rows, int32_t n_cols, const float* target_values, int32_t* index,
+                   float* value, float* row_max, void* stream) {
+    if (n_rows < 0 || n_cols < 1 || (n_rows > 0 && (!rows || !index)))
+        return set_err(CBN_E_ARG, "cbn_row_argmax: bad arguments");
+    if (n_rows == 0) return CBN_OK;
+    const ArgmaxOut am = {target_values, index, value, row_max};
+    return launch_row_argmax(rows, (long long)n_rows, (int)n_cols, am, reinterpret_cast<hipStream_t>(stream));
+}
+
+int64_t cbn_plan_argmax_scratch(const cbn_plan* plan, int64_t n_queries) {
+    if (!plan || n_queries < 0 || argmax_native(plan)) return 0;
+    return n_queries * (int64_t)plan->N;
+}
+
+int cbn_plan_run_argmax(cbn_plan* plan, int64_t n_queries, const float* const* evidence, int32_t n_evidence,
+                        const float* target_values, int32_t* index, float* value, float* row_max, float* scratch,
+                        int32_t flags, void* stream) {
+    if (!plan) return set_err(CBN_E_ARG, "null plan");
+    if (!index) return set_err(CBN_E_ARG, "cbn_plan_run_argmax: null output");
+    if (n_queries <= 0) return set_err(CBN_E_ARG, "cbn_plan_run_argmax: needs >= 1 query");
+    if (n_evidence < 0 || (n_evidence > 0 && !evidence)) return set_err(CBN_E_ARG, "cbn_plan_run_argmax: null evidence");
+    for (int i = 0; i < n_evidence; ++i)
+        if (!evidence[i]) return set_err(CBN_E_ARG, "null evidence column %d", i);
+    const bool native = argmax_native(plan);
+    if (!native && !scratch)
+        return set_err(CBN_E_ARG, "cbn_plan_run_argmax: this plan needs cbn_plan_argmax_scratch floats of scratch");
+    const bool table = !plan->param && !plan->direct;
+    if (table) {
+        if (n_evidence != plan->ns) return set_err(CBN_E_ARG, "plan expects %d evidence columns, got %d", plan->ns, n_evidence);
+        if (!plan->d_fac || !plan->d_slots || !plan->d_image || !plan->d_sync)
+            return set_err(CBN_E_ARG, "plan has no device buffers");
+    }
+    if (plan->h_status && __atomic_load_n(plan->h_status, __ATOMIC_ACQUIRE)) {
+        __atomic_store_n(plan->h_status, 0u, __ATOMIC_RELEASE);
+        return set_err(CBN_E_TIMEOUT, "an earlier single-launch call of this plan timed out in its grid barrier "
+                                      "(not every block was resident); its rows are NaN");
+    }
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const ArgmaxOut am = {target_values, index, value, row_max};
+    int rc;
+    if (!table) {
+        // direct / parametric plans: their raw launch (per-block maxima into the plan's own words, unused here)
+        rc = cbn_plan_run(plan, n_queries, evidence, n_evidence, plan->d_sync + kMaxWordOff, scratch,
+                          (flags & CBN_RUN_BUILD_TABLES) | CBN_RUN_RAW, stream);
+        if (rc) return rc;
+        return launch_row_argmax(scratch, (long long)n_queries, plan->N, am, s);
+    }
+    if (flags & CBN_RUN_BUILD_TABLES) {
+        rc = cbn_plan_build_tables(plan, stream);
+        if (rc) return rc;
+    }
+    if (!native) {
+        // generic table plans: the write pass dividing by 1.0f stores the raw rows (IEEE x / 1 = x)
+        rc = cbn_plan_query_write(plan, n_queries, evidence, n_evidence, plan->d_sync + kOneWordOff, scratch, stream);
+        if (rc) return rc;
+        return launch_row_argmax(scratch, (long long)n_queries, plan->N, am, s);
+    }
+    EvPtrs ev;
+    memset(&ev, 0, sizeof(ev));
+    for (int i = 0; i < n_evidence; ++i) ev.p[i] = evidence[i];
+    if (plan->use_lds)
+        return plan->vpl == 2 ? launch_argmax_v<2, true>(plan, n_queries, ev, am, s)
+                              : launch_argmax_v<1, true>(plan, n_queries, ev, am, s);
+    return plan->vpl == 2 ? launch_argmax_v<2, false>(plan, n_queries, ev, am, s)
+                          : launch_argmax_v<1, false>(plan, n_queries, ev, am, s);
+}
+
 int cbn_plan_status(cbn_plan* plan, int32_t* status) {
     if (!plan || !status) return set_err(CBN_E_ARG, "cbn_plan_status: bad arguments");
     unsigned v = 0;
@@ -3525,7 +3782,8 @@ int32_t cbn_plan_flags(const cbn_plan* plan) {
            (plan->paired ? CBN_PLAN_PAIRED : 0) | (plan->staged ? CBN_PLAN_STAGED : 0) |
            (plan->fused_ok ? CBN_PLAN_FUSED : 0) | (plan->param ? CBN_PLAN_PARAMETRIC : 0) |
            (plan->vpl == 2 ? CBN_PLAN_VPL2 : 0) | (plan->direct ? CBN_PLAN_DIRECT : 0) |
-           (plan->cols ? CBN_PLAN_COLS : 0) | (plan->slots ? CBN_PLAN_SLOTS : 0);
+           (plan->cols ? CBN_PLAN_COLS : 0) | (plan->slots ? CBN_PLAN_SLOTS : 0) |
+           (argmax_native(plan) ? CBN_PLAN_ARGMAX : 0);
 }
 
 int32_t cbn_plan_max_words(const cbn_plan* plan) {

@@ -23,6 +23,7 @@ constexpr int kFastPtrs = 416;  // fast table path: 104 factors x 4 observed par
 // its own 8-byte slot and every block polls all of them.
 constexpr int kSyncLine = 32;
 constexpr int kHostStatusWordOff = 8;  // words 8-9 of line 0: device address of the plan's host-mapped status
+constexpr int kOneWordOff = 12;  // word 12 of line 0 (table plans): the bits of 1.0f (cbn_plan_run_argmax)
 constexpr int kMaxSlots = 1024;
 constexpr int kSlotWordOff = kSyncLine;
 // then the max/raw passes' per-block maxima (one word per block; the

@@ -130,6 +130,39 @@ py::object run(uintptr_t fn, uintptr_t plan, py::dict evidence, py::tuple slots,
     return py::cast(out);
 }
 
+// InferenceEngine.predict's hot path: run's evidence checks, then index (int32
+// [Q]), value and row_max (float32 [Q]) -- plus `scratch_per_query` floats of
+// scratch per query for plans without the arg-max epilogue
+// (cbn_plan_argmax_scratch) -- and ONE call of cbn_plan_run_argmax (passed in
+// as `fn`) on the current stream.  tv_ptr: the target's float32 sample points
+// on the device, or 0 (value is then left to the caller's gather).  Returns
+// (index, value, row_max); None when a fast check failed; an int = the C ABI's
+// error code.
+using argmax_fn = int (*)(void*, int64_t, const float* const*, int32_t, const float*, int32_t*, float*, float*, float*,
+                          int32_t, hipStream_t);
+
+py::object run_argmax(uintptr_t fn, uintptr_t plan, py::dict evidence, py::tuple slots, py::object first,
+                      int64_t device_index, bool target_observed, uintptr_t tv_ptr, int64_t scratch_per_query,
+                      int32_t flags) {
+    Cols c;
+    if (!gather(evidence, slots, first, device_index, target_observed, c)) return py::none();
+    const auto dev = at::Device(at::kCUDA, (c10::DeviceIndex)device_index);
+    const auto fopt = at::TensorOptions().dtype(at::kFloat).device(dev);
+    at::Tensor index = at::empty({c.n}, at::TensorOptions().dtype(at::kInt).device(dev));
+    at::Tensor value = at::empty({c.n}, fopt);
+    at::Tensor row_max = at::empty({c.n}, fopt);
+    at::Tensor scratch;  // (freed at return: stream-ordered behind the launches that use it)
+    if (scratch_per_query > 0) scratch = at::empty({c.n * scratch_per_query}, fopt);
+    const hipStream_t s = c10::hip::getCurrentHIPStream(device_index).stream();
+    const int rc = reinterpret_cast<argmax_fn>(fn)(
+        reinterpret_cast<void*>(plan), c.n, c.p, (int32_t)PyTuple_GET_SIZE(slots.ptr()),
+        reinterpret_cast<const float*>(tv_ptr), static_cast<int32_t*>(index.data_ptr()),
+        static_cast<float*>(value.data_ptr()), static_cast<float*>(row_max.data_ptr()),
+        scratch.defined() ? static_cast<float*>(scratch.data_ptr()) : nullptr, flags, s);
+    if (rc) return py::int_(rc);
+    return py::make_tuple(index, value, row_max);
+}
+
 using scale_fn = int (*)(float*, int64_t, const unsigned*, int32_t, hipStream_t);
 using scale_batch_fn = int (*)(float* const*, const int64_t*, int32_t, const unsigned*, int32_t, hipStream_t);
 
@@ -1190,6 +1223,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("redraw", &redraw);
     m.doc() = "cbn MI355X host fast path (cached-plan infer)";
     m.def("run", &run);
+    m.def("run_argmax", &run_argmax);
     m.def("scale", &scale);
     m.def("nccl_unique_id", &nccl_unique_id);
     m.def("nccl_comm_init", &nccl_comm_init);

@@ -7,6 +7,10 @@ step between the two query passes: an all-reduce(MAX) of a single 4-byte word
 float order).  Re-assembling the marginal tensor on every rank is optional
 (``gather=True``: all-gather of the [q_r, N] shards over xGMI); without it each
 rank keeps the rows it owns.
+
+Predictions need none of this: ``predict`` (the per-query arg-max of the
+marginal) never uses the batch max, and rows are independent, so a rank calls
+``bn.predict`` on its own shard and no collective is involved.
 """
 from __future__ import annotations
 

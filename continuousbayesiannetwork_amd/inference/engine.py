@@ -18,6 +18,11 @@ sample-domain index arrays, device image) is cached per
 deterministic (N_max <= |domain|).  When the reference would draw random
 padding values (node.py:302-333) the plan is rebuilt on every call, consuming
 Python's ``random`` in the reference's order, so results stay identical.
+
+``predict`` returns what the reference's consumers take from that result --
+per query, the arg-max of the row and the target's sample point there
+(bayesian_network.py:329-373) -- from the same plans in one launch that needs
+neither the global max nor the [n_queries, N] output (cbn_plan_run_argmax).
 """
 from __future__ import annotations
 
@@ -210,7 +215,7 @@ class _FastPath:
     """Everything the hot path needs for one cached (target, evidence keys, N)."""
 
     __slots__ = ("plan", "device", "first", "ptrs", "max_ptr", "lib", "tdom", "host", "run_fn", "slot_keys",
-                 "scale_fn", "host_scale", "words", "redraw", "runner")
+                 "scale_fn", "host_scale", "words", "redraw", "runner", "argmax")
 
     def __init__(self, plan: "Plan", device: torch.device, first_key):
         self.plan = plan
@@ -230,6 +235,7 @@ class _FastPath:
         nw = self.lib.cbn_plan_max_words(plan.handle)
         self.words = torch.zeros(nw, dtype=torch.int32, device=device) if nw > 0 else None
         self.runner = None  # native Runner of this fast path (InferenceEngine._runner), built on first use
+        self.argmax = None  # predict: (host_fast.run_argmax, cbn_plan_run_argmax, scratch floats per query)
 
 
 class InferenceEngine:
@@ -961,6 +967,131 @@ class InferenceEngine:
         if rc:
             _native.check(rc, "cbn_plan_run")
         return out, tdom
+
+    # ------------------------------------------------------------- predict --
+    def predict(self, target: str, evidence: Dict[str, torch.Tensor], N_max: int):
+        """Per query, the arg-max of the target's marginal: ``(index, value,
+        row_max)``, int32 / float [n_queries] tensors on the device -- what
+        every consumer of ``infer`` in the reference computes from its [Q, N]
+        result (bayesian_network.py:329-373: ``argmax`` over each row, gather
+        of the domain value), in one launch with no grid barrier, no division
+        and no [Q, N] output (cbn_plan_run_argmax, include/cbn_amd.h).
+
+        ``index[q]`` is the first index of the maximum of the UNNORMALISED
+        product row -- the row ``infer_raw`` returns: ties go to the lowest
+        column, a NaN is greater than every number (the first NaN wins),
+        -0.0 == +0.0, an all-zero row (off-domain evidence) gives 0, as
+        ``torch.argmax``.  ``value[q]`` is ``target_domain[index[q]]`` (this
+        call's draw when the domain is redrawn), ``row_max[q]`` the
+        unnormalised maximum itself.
+
+        This is not ``argmax(infer(...)[0], dim=1)``: dividing by the positive
+        batch max does not move a row's arg-max, but two distinct raw values
+        can divide to the same float, and the normalised form then picks the
+        earlier column.  The two agree whenever the row's top entry is
+        separated from the others.
+
+        Takes and rejects exactly the calls ``infer`` does (same plan cache,
+        redraw handling, [Q, N] column routing, conversions and errors)."""
+        plan, fp = self.call_plan(target, evidence, N_max)  # evidence=None raises AttributeError, as infer
+        device = fp.device if fp is not None else _native.require_gpu(self.bn.device)
+        try:
+            if fp is not None:
+                res = self._predict_fast(fp, evidence)
+                if res is not None:
+                    return res
+            n_queries = next(iter(evidence.values())).shape[0] if len(evidence) > 0 else 1
+            return self._predict(plan, dict(evidence.items()), n_queries, device)
+        finally:
+            if fp is None:  # a plan rebuilt per call
+                torch.cuda.current_stream(device).synchronize()
+                plan.destroy()
+
+    @staticmethod
+    def _target_values(plan: Plan, device) -> int:
+        """Device address of the plan's target sample points when the kernels
+        can read them (contiguous float32 on the plan's device), else 0 (the
+        caller gathers in torch)."""
+        t = plan.target_domain
+        ok = t.dtype is torch.float32 and t.device == device and t.is_contiguous() and t.numel() == plan.n_samples
+        return t.data_ptr() if ok else 0
+
+    def _predict_fast(self, fp: "_FastPath", evidence):
+        """predict's hot path (host_fast.run_argmax: the native evidence checks,
+        the outputs, one library call); None when those checks reject the
+        evidence (conversions / the reference's errors: ``_predict``)."""
+        plan = fp.plan
+        if fp.argmax is None:
+            fn = ctypes.cast(fp.lib.cbn_plan_run_argmax, ctypes.c_void_p).value
+            fp.argmax = (_native.load_host().run_argmax, fn, int(fp.lib.cbn_plan_argmax_scratch(plan.handle, 1)))
+        host, fn, per_q = fp.argmax
+        tv = self._target_values(plan, fp.device)
+        built = plan.tables_built
+        flags = self._flags(plan) & _native.CBN_RUN_BUILD_TABLES
+        res = host(fn, plan.handle.value, evidence, fp.slot_keys, fp.first, fp.device.index, plan.target_observed,
+                   tv, per_q, flags)
+        if res is None:  # nothing launched
+            plan.tables_built = built
+            return None
+        if type(res) is int:
+            _native.check(res, "cbn_plan_run_argmax")
+        index, value, row_max = res
+        if not tv:
+            value = plan.target_domain.to(fp.device)[index.long()]
+        return index, value, row_max
+
+    def _predict(self, plan: Plan, evidence, n_queries: int, device):
+        """predict's general path, as ``_run``: [Q, N] columns on the wide
+        direct plan, conversions, the reference's shape errors -- all raised
+        before anything is launched."""
+        lib = _native.load()
+        N = plan.n_samples
+        wide = self._wide(plan, evidence)
+        run_plan = plan
+        if wide:
+            run_plan = self._wide_plan(plan, wide, device)
+            cols = []
+            for v in plan.slots:
+                t = evidence[v]
+                if t.device != device or t.dtype != torch.float32 or not t.is_contiguous():
+                    t = t.to(device=device, dtype=torch.float32).contiguous()
+                cols.append(t)
+        else:
+            cols = self._columns(plan, evidence, n_queries, device)
+        tq = n_queries if plan.target_observed else 1
+        if (n_queries, N) != (tq, plan.target_domain.numel()):
+            raise AssertionError("pdf and domain must have same shape.")
+        if n_queries == 0:
+            raise RuntimeError("max(): Expected reduction dim to be specified for input.numel() == 0.")
+        if wide:
+            flags = 0
+            if not run_plan.tables_built or not plan.deterministic:  # (a redrawn plan's constant rows: this call's draws)
+                flags = _native.CBN_RUN_BUILD_TABLES
+                run_plan.tables_built = True
+        else:
+            flags = self._flags(plan) & _native.CBN_RUN_BUILD_TABLES
+        index = torch.empty(n_queries, dtype=torch.int32, device=device)
+        value = torch.empty(n_queries, dtype=torch.float32, device=device)
+        row_max = torch.empty(n_queries, dtype=torch.float32, device=device)
+        ns = int(lib.cbn_plan_argmax_scratch(run_plan.handle, n_queries))
+        scratch = torch.empty(ns, dtype=torch.float32, device=device) if ns > 0 else None
+        tv = self._target_values(plan, device)
+        ptrs = (ctypes.c_void_p * max(1, len(cols)))(*[c.data_ptr() for c in cols])
+        with torch.cuda.device(device):
+            _native.check(lib.cbn_plan_run_argmax(run_plan.handle, n_queries, ptrs, len(cols), tv or None,
+                                                  _native.ptr(index), _native.ptr(value), _native.ptr(row_max),
+                                                  _native.ptr(scratch) if scratch is not None else None, flags,
+                                                  _native.stream_ptr(device)), "cbn_plan_run_argmax")
+        if not tv:
+            value = plan.target_domain.to(device)[index.long()]
+        return index, value, row_max
+
+    def predict_flags(self, target: str, evidence_keys, N_max: int) -> int:
+        """cbn_plan_flags of the cached (target, evidence keys, N) plan (0: none
+        cached): which kernel serves it, and CBN_PLAN_ARGMAX when its arg-max
+        runs in the query kernel."""
+        fp = self._fast.get((target, tuple(evidence_keys), N_max))
+        return int(_native.load().cbn_plan_flags(fp.plan.handle)) if fp else 0
 
     def timing(self):
         """(calls, avg max-pass ms, avg write-pass ms) over the timed calls of every cached plan."""

@@ -40,3 +40,13 @@ class VariableElimination(ExactInference):
     def query(self, target_node: str, evidence: Optional[Dict[str, torch.Tensor]] = None, N_max: int = 16,
               do: Optional[List[str]] = None):
         return self.infer(target_node, evidence, do, N_max=N_max)
+
+    def map_query(self, target_node: str, evidence: Optional[Dict[str, torch.Tensor]] = None, N_max: int = 16,
+                  do: Optional[List[str]] = None):
+        """The maximum a posteriori sample point of ``target_node`` per evidence
+        row and its index: ``(value, index)`` of ``BayesianNetwork.predict``
+        (the arg-max bayesian_network.py:329-373 takes from ``infer``'s
+        result).  ``do`` is accepted and ignored, as in ``infer``."""
+        if self.bn is None:
+            raise ValueError("ExactInference needs the BayesianNetwork (bn=...) it runs on")
+        return self.bn.predict(target_node, evidence, N_max=N_max, return_index=True)

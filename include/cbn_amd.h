@@ -243,6 +243,45 @@ int cbn_plan_run_fold(cbn_plan* plan, int64_t n_queries, const float* const* evi
                       const uint32_t* fold_words, int32_t fold_n_words, int32_t flags, void* stream);
 int cbn_plan_status(cbn_plan* plan, int32_t* status);
 
+/* ---- prediction: per query, the arg-max of the marginal.
+ * Replaces what BayesianNetwork.benchmarking_df does with every infer result
+ * (bayesian_network.py:329-373: argmax over each row of the [Q, N] pdf, gather
+ * of the target's domain value at that index).  Per query row q of the
+ * UNnormalised product (the rows of a CBN_RUN_RAW launch; dividing by the
+ * positive batch max does not move a row's arg-max):
+ *   index[q]   : first index of the row maximum -- ties to the lowest column,
+ *                a NaN greater than every number (the first NaN wins),
+ *                -0 == +0, an all-zero row (off-domain evidence) gives 0:
+ *                torch.argmax's rules
+ *   value[q]   : target_values[index[q]] (target_values: device [N], the
+ *                target's sample points; not written when either is NULL)
+ *   row_max[q] : the unnormalised row maximum (NULL: not written)
+ * No grid barrier, no division, no [Q, N] output on plans with
+ * CBN_PLAN_ARGMAX.  All three added in ABI 5 (additive). */
+
+/* One launch on plans with CBN_PLAN_ARGMAX (the query kernel reduces each row
+ * in registers); other plans store their raw rows in `scratch` (device,
+ * cbn_plan_argmax_scratch floats; CBN_E_ARG when needed and NULL) and reduce
+ * them with cbn_row_argmax's kernel.  flags: CBN_RUN_BUILD_TABLES only.
+ * n_queries >= 1; evidence as cbn_plan_run.  Reports (and clears) a pending
+ * grid-barrier timeout of the plan as cbn_plan_run does. */
+int cbn_plan_run_argmax(cbn_plan* plan, int64_t n_queries, const float* const* evidence, int32_t n_evidence,
+                        const float* target_values /* device [N] or NULL */, int32_t* index,
+                        float* value /* NULL ok */, float* row_max /* NULL ok */, float* scratch, int32_t flags,
+                        void* stream);
+
+/* Floats of scratch cbn_plan_run_argmax needs for n_queries (0 on plans with
+ * CBN_PLAN_ARGMAX).  No reference counterpart (bayesian_network.py:329-373
+ * keeps the whole pdf). */
+int64_t cbn_plan_argmax_scratch(const cbn_plan* plan, int64_t n_queries);
+
+/* The same three outputs from stored rows [n_rows, n_cols] (row-major float32,
+ * device): the argmax + gather of bayesian_network.py:329-373 in one launch,
+ * with the full comparison rules above (rows of parametric plans can hold NaN
+ * and inf).  16-B loads when n_cols % 4 == 0 and rows is 16-B aligned. */
+int cbn_row_argmax(const float* rows, int64_t n_rows, int32_t n_cols, const float* target_values, int32_t* index,
+                   float* value, float* row_max, void* stream);
+
 /* CBN_E_TIMEOUT (and clears the report) if a single-launch call of the plan
  * timed out in its grid barrier since the last report, else CBN_OK: a read of
  * the plan's host-mapped status word, no device round trip.  A caller that
@@ -262,6 +301,7 @@ int cbn_plan_check(cbn_plan* plan);
 #define CBN_PLAN_DIRECT 128    /* direct plan (cbn_plan_create_direct) */
 #define CBN_PLAN_COLS 256      /* k_query_cols (evidence indexed once per slot; non-paired table plans) */
 #define CBN_PLAN_SLOTS 512     /* k_query_slots (slot-indexed evidence, global tables, >= 4 lanes per query; round 5) */
+#define CBN_PLAN_ARGMAX 1024   /* cbn_plan_run_argmax runs in the query kernel itself (no rows stored) */
 int32_t cbn_plan_flags(const cbn_plan* plan);
 
 /* Test hook: mark the plan as if a single-launch call had timed out in its
