@@ -76,6 +76,31 @@ def chain_data(n, d, S, seed, values=None, noise=(0.6, 0.3, 0.1), stay=None):
     return vals[X], cols, edges
 
 
+def skewed_chain(n, d, S, seed, stay=0.5, hot=5, p_hot=0.9):
+    """Discrete chain X0 -> ... -> X{n-1} for PARTIAL evidence.  A "fresh" draw
+    is ``hot`` with probability ``p_hot``, else uniform on 0..d-1; X0 is a
+    fresh draw and X_i = X_{i-1} with probability ``stay``, else a fresh draw.
+    A factor whose parent is free is the mean of its CPD over the parent's d
+    sample points: with ``chain_data(stay=...)``'s uniform draws that mean is
+    about 1 / d in every column, and a chain with many free nodes leaves fp32
+    range (tests/parity.py then refuses the reference); here the ``hot``
+    column keeps about ``p_hot (1 - stay)`` per such factor.  Every column
+    holds all d levels (asserted), so N_max = d redraws nothing."""
+    rng = np.random.default_rng(seed)
+
+    def fresh():
+        return np.where(rng.random(S) < p_hot, hot, rng.integers(0, d, S))
+
+    X = np.zeros((S, n), np.int64)
+    X[:, 0] = fresh()
+    for i in range(1, n):
+        X[:, i] = np.where(rng.random(S) < stay, X[:, i - 1], fresh())
+    assert all(np.unique(X[:, i]).size == d for i in range(n)), "a column misses a level: raise S or lower p_hot"
+    cols = [f"X{i}" for i in range(n)]
+    edges = [(f"X{i}", f"X{i+1}") for i in range(n - 1)]
+    return X.astype(np.float32), cols, edges
+
+
 def random_dag_data(n, d, max_parents, S, seed):
     """Random DAG over X0..X{n-1} (edges only from lower to higher index)."""
     rng = np.random.default_rng(seed)

@@ -17,6 +17,10 @@ oracle's rows:
 * ``value == domain[index]`` exactly;
 * the helper REFUSES a comparison in which fewer than 90 % of the rows are
   decided (it would check little).
+
+``check_exact`` is the GPU tests' other check: ``predict`` against the same
+plan's ``infer_raw`` rows, bit for bit (tests/test_gpu_predict.py,
+tests/test_gpu_staged_shapes.py).
 """
 import numpy as np
 
@@ -50,6 +54,44 @@ def decided(raw):
         return fin & (zero | (safe[:, 0] >= MIN_TOP))
     two = np.sort(safe, axis=1)[:, -2:]  # (the runner-up, the top): a tie makes them equal
     return fin & (zero | ((two[:, 1] >= MIN_TOP) & (two[:, 0] < (1 - MARGIN) * two[:, 1])))
+
+
+def check_exact(bn, target, evt, N, seed=None):
+    """``engine.predict`` against the same plan's own rows, exactly: ``index ==
+    torch.argmax(rows, 1)`` and ``row_max == rows.max(1).values`` bit for bit on
+    EVERY row, where ``rows`` are ``engine.infer_raw``'s.  Plans without a raw
+    launch (generic table plans, redrawn domains) are compared with ``infer``'s
+    rows instead, on decided rows.  ``evt``: device evidence columns; ``seed``:
+    Python's ``random`` before each call (redrawn domains).  Returns (index,
+    value, row_max) as numpy plus whether the plan had raw rows to compare
+    with."""
+    import random
+
+    import torch
+
+    def bits(t):
+        return t.contiguous().view(torch.int32)
+
+    eng = bn.engine
+    random.seed(seed)
+    index, value, row_max = eng.predict(target, evt, N)
+    assert index.dtype == torch.int32 and value.dtype == torch.float32 and row_max.dtype == torch.float32
+    random.seed(seed)
+    res = eng.infer_raw(target, evt, N)
+    if res is not None:
+        rows = res[0]
+        assert torch.equal(index.long(), torch.argmax(rows, 1))
+        mx = rows.max(1).values
+        nan = torch.isnan(mx)
+        assert torch.equal(torch.isnan(row_max), nan)
+        assert torch.equal(bits(row_max)[~nan], bits(mx)[~nan])
+    else:
+        random.seed(seed)
+        rows, _ = bn.infer(target, evt, N_max=N)
+        dec = torch.tensor(decided(rows.cpu().numpy()), device=rows.device)
+        assert dec.float().mean() >= 0.9
+        assert torch.equal(index.long()[dec], torch.argmax(rows, 1)[dec])
+    return index.cpu().numpy(), value.cpu().numpy(), row_max.cpu().numpy(), res is not None
 
 
 def assert_predictions(index, value, row_max, raw_ref, domain, n_factors=1, peak=1.0, min_decided=MIN_DECIDED):

@@ -30,7 +30,7 @@ from golden_io import load_param_golden, oracle_estimators
 from helpers import chain_data, continuous_data, make_bn, param_config, sample_evidence, special_batch
 from oracle.ref_infer import OracleBN
 from parity import n_factors, peak
-from predict_ref import assert_predictions, decided, raw_argmax
+from predict_ref import assert_predictions, check_exact, decided, raw_argmax
 from test_gpu_param import load_fixture_params
 
 pytestmark = pytest.mark.gpu
@@ -46,38 +46,9 @@ def _t(ev, dev):
     return {k: torch.tensor(v, device=dev) for k, v in ev.items()}
 
 
-def _bits(t):
-    return t.contiguous().view(torch.int32)
-
-
 def _flags(bn):
     lib = _native.load()
     return [int(lib.cbn_plan_flags(p.handle)) for p in bn.engine._plans.values()]
-
-
-def check_exact(bn, target, evt, N, seed=None):
-    """Check (i); returns (index, value, row_max) as numpy plus whether the
-    plan had raw rows to compare with."""
-    eng = bn.engine
-    random.seed(seed)
-    index, value, row_max = eng.predict(target, evt, N)
-    assert index.dtype == torch.int32 and value.dtype == torch.float32 and row_max.dtype == torch.float32
-    random.seed(seed)
-    res = eng.infer_raw(target, evt, N)
-    if res is not None:
-        rows = res[0]
-        assert torch.equal(index.long(), torch.argmax(rows, 1))
-        mx = rows.max(1).values
-        nan = torch.isnan(mx)
-        assert torch.equal(torch.isnan(row_max), nan)
-        assert torch.equal(_bits(row_max)[~nan], _bits(mx)[~nan])
-    else:
-        random.seed(seed)
-        rows, _ = bn.infer(target, evt, N_max=N)
-        dec = torch.tensor(decided(rows.cpu().numpy()), device=rows.device)
-        assert dec.float().mean() >= 0.9
-        assert torch.equal(index.long()[dec], torch.argmax(rows, 1)[dec])
-    return index.cpu().numpy(), value.cpu().numpy(), row_max.cpu().numpy(), res is not None
 
 
 def check_oracle(out, ora, target, ev, N, seed=None):

@@ -97,7 +97,10 @@ CASES = {
     # branch's binary search), more than one 128-query unit and a ragged end
     "staged": (lambda: chain_data(6, 32, 30000, 15, stay=0.8), "X5", 32, 421, FAST | LDS | PAIRED | STAGED,
                COLS | SLOTS, False, None),
-    # k_query_staged: a factor with two observed parents (the second evidence load)
+    # k_query_staged: a factor with two observed parents (the second evidence load).  Plan.order is
+    # X0, R, X1, X2, X3, X4: R sits IN FRONT of the product (X0 and R are the prefix merged into X1's
+    # table), so no 1-row factor is staged here -- the kernel's n_obs == 0 branch is covered by
+    # tests/test_gpu_staged_shapes.py (cases A, C, D_prefix9)
     "staged_two_parents": (lambda: _chain_with_small_root(30000, 16), "X4", 32, 421, FAST | LDS | PAIRED | STAGED,
                            COLS | SLOTS, False, 7),
 }
