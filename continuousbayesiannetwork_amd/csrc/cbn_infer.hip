@@ -319,7 +319,12 @@ __device__ unsigned g_clock_n = 0;
             g_clock_n = _i + 1;                                                               \
         }                                                                                     \
     } while (0)
+// a helper that stamps takes the wave's buffer pointer as its last parameter
+#define CBN_STAMP_PARAM , unsigned long long* const _stp
+#define CBN_STAMP_ARG , _stp
 #else
+#define CBN_STAMP_PARAM
+#define CBN_STAMP_ARG
 #define CBN_STAMP_INIT do {} while (0)
 #define CBN_STAMP(k) do {} while (0)
 #define CBN_CLOCK_END do {} while (0)
@@ -826,6 +831,113 @@ __device__ __forceinline__ unsigned slot_barrier_max(unsigned* __restrict__ sync
     return slot_poll_max<kMaxSlots / kWave>(sync, epoch);
 }
 
+// ---- mode epilogues of the fast-path query kernels ------------------------
+// k_query_fast / _cols / _slots / _staged are each compiled once per mode:
+//   kModeMax     per-block maxima of the products -> max_out[block]
+//   kModeWrite   rows = products / max(max_in[0, n_max)), the max published in *max_out
+//   kModeFused   both in one launch: the products wait in registers for the grid barrier
+//   kModeRaw     the unnormalised rows and the per-block maxima (a scale pass divides)
+//   kModeArgmax  per query the first column of the row maximum (ArgmaxOut), no rows
+// What a mode does with a lane's products is the same in every kernel and lives
+// here.  lane / wid / tid / nthr are the caller's own values (k_query_fast
+// reads blockDim, the others know it at compile time).
+
+// kModeWrite: the batch max of the max pass's per-block words (or of one
+// all-reduced word).  Every wave reduces them itself (L2 hits, no block sync);
+// block 0 publishes the max.
+__device__ __forceinline__ float batch_max(const unsigned* __restrict__ max_in, int n_max,
+                                           unsigned* __restrict__ max_out, int lane, int tid) {
+    unsigned m = 0;
+    for (int i = lane; i < n_max; i += kWave) m = max(m, max_in[i]);
+    m = wave_max_u(m);
+    if (max_out && blockIdx.x == 0 && tid == 0) *max_out = m;
+    return __uint_as_float(m);
+}
+
+// A lane's 4 VPL products acc[4 v + i] -> columns col[v] + i of row o, 16-B stores.
+template <int VPL>
+__device__ __forceinline__ void store_row(float* o, const int (&col)[VPL], const float (&acc)[4 * VPL]) {
+#pragma unroll
+    for (int v = 0; v < VPL; ++v)
+        *reinterpret_cast<float4*>(o + col[v]) = make_float4(acc[4 * v], acc[4 * v + 1], acc[4 * v + 2], acc[4 * v + 3]);
+}
+// ... divided by the batch max: the IEEE quotient per element (bayesian_network.py:296)
+template <int VPL>
+__device__ __forceinline__ void store_row_div(float* o, const int (&col)[VPL], const float (&acc)[4 * VPL],
+                                              float maxv) {
+#pragma unroll
+    for (int v = 0; v < VPL; ++v)
+        *reinterpret_cast<float4*>(o + col[v]) =
+            make_float4(acc[4 * v] / maxv, acc[4 * v + 1] / maxv, acc[4 * v + 2] / maxv, acc[4 * v + 3] / maxv);
+}
+
+// End of one round of products.  Called by EVERY lane of the wave (the arg-max
+// reduction needs them all); `valid`: the lane holds query q of the batch,
+// `ok`: and may store its row.  Write stores the divided row, Raw the row as
+// it is, and every mode that needs a max folds the products into lmax.  A
+// fused launch's rows are stored after its barrier, by the kernel: `hold`
+// (block-uniform) notes in fq that acc is the row of query q.
+template <int VPL, int MODE>
+__device__ __forceinline__ void round_epilogue(const float (&acc)[4 * VPL], const int (&col)[VPL], int l, int L, bool valid,
+                                               bool ok, long long q, int N, float* out, float maxv, float& lmax,
+                                               bool hold, long long& fq, const ArgmaxOut& am) {
+    if (MODE == kModeArgmax) argmax_store<VPL>(acc, col, l, L, valid, q, am);
+    if (ok) {
+        if (MODE == kModeFused && hold) fq = q;
+        if (MODE == kModeWrite) {
+            store_row_div<VPL>(out + q * N, col, acc, maxv);
+        } else if (MODE == kModeRaw) {
+            store_row<VPL>(out + q * N, col, acc);
+#pragma unroll
+            for (int i = 0; i < 4 * VPL; ++i) lmax = fmaxf(lmax, acc[i]);
+        } else if (MODE != kModeArgmax) {
+#pragma unroll
+            for (int i = 0; i < 4 * VPL; ++i) lmax = fmaxf(lmax, acc[i]);
+        }
+    }
+}
+
+// kModeMax / kModeRaw: the block's max -> max_out[block] (one word per block,
+// plain store).  Block 0 also zeroes the words [gridDim.x, n_max) of blocks
+// this launch does not have: an earlier, larger launch may have left them set.
+__device__ __forceinline__ void publish_block_max(float lmax, float* wmax, unsigned* __restrict__ max_out, int n_max,
+                                                  int lane, int wid, int tid, int nthr) {
+    lmax = wave_max(lmax);
+    if (lane == 0) wmax[wid] = lmax;
+    __syncthreads();
+    if (tid == 0) {
+        float m = 0.f;
+        for (int i = 0; i < nthr / kWave; ++i) m = fmaxf(m, wmax[i]);
+        max_out[blockIdx.x] = __float_as_uint(m);
+    }
+    if (blockIdx.x == 0)
+        for (int i = (int)gridDim.x + tid; i < n_max; i += nthr) max_out[i] = 0u;
+}
+
+// kModeFused: block max -> grid barrier -> the batch max, in every thread (NaN
+// after a barrier timeout).  Block 0 publishes it in *max_out.  The caller
+// then stores its held rows with store_row_div.  (k_query_staged has its own
+// form of this tail: DPP reductions and a reciprocal multiply, measured there.)
+__device__ __forceinline__ float fused_block_max(float lmax, float* wmax, unsigned* __restrict__ sync, unsigned epoch,
+                                                 unsigned* __restrict__ max_out, int lane, int wid,
+                                                 int nthr CBN_STAMP_PARAM) {
+    lmax = wave_max(lmax);
+    if (lane == 0) wmax[wid] = lmax;
+    __syncthreads();
+    if (wid == 0) {
+        const int nw = nthr / kWave;
+        const unsigned gm = slot_barrier_max(sync, epoch, wave_max(lane < nw ? wmax[lane] : 0.f));
+        if (lane == 0) {
+            wmax[0] = __uint_as_float(gm);
+            if (blockIdx.x == 0 && max_out) *max_out = gm;
+        }
+    }
+    CBN_STAMP(8);
+    __syncthreads();
+    CBN_STAMP(9);
+    return wmax[0];
+}
+
 template <int VPL, bool USE_LDS, int MODE, int NP>
 __global__ void __launch_bounds__(kQueryThreads)
 k_query_fast(int rec_off, int nf, int ns, const float* __restrict__ gimage, int image_floats, FPtrsT<NP> fp,
@@ -871,15 +983,7 @@ k_query_fast(int rec_off, int nf, int ns, const float* __restrict__ gimage, int 
     const int lsh = __builtin_ctz(L);  // L: a power of two (query index = item >> lsh)
 
     float maxv = 1.f;
-    if (MODE == kModeWrite) {
-        // the max pass's per-block maxima (or one all-reduced word): every wave
-        // reduces them itself (L2 hits, no block sync)
-        unsigned m = 0;
-        for (int i = lane; i < n_max; i += kWave) m = max(m, max_in[i]);
-        m = wave_max_u(m);
-        maxv = __uint_as_float(m);
-        if (max_out && blockIdx.x == 0 && tid == 0) *max_out = m;
-    }
+    if (MODE == kModeWrite) maxv = batch_max(max_in, n_max, max_out, lane, tid);
     float lmax = 0.f;
     const int qi = lane / L;  // query slot of this lane within the wave
     const int l = lane - qi * L;
@@ -1100,68 +1204,17 @@ k_query_fast(int rec_off, int nf, int ns, const float* __restrict__ gimage, int 
             }
         }
         if (first) CBN_STAMP(5);
-        if (MODE == kModeArgmax) argmax_store<VPL>(acc, col, l, L, valid, q, am);  // (wave-uniform call site)
-        if (valid && CBN_OK_OR(q < Q && (long long)(l + 1) * VPL * 4 <= N, 3)) {
-            if (MODE == kModeFused) fq = q;
-            if (MODE == kModeWrite) {
-                float* o = out + q * N;
-#pragma unroll
-                for (int v = 0; v < VPL; ++v)
-                    *reinterpret_cast<float4*>(o + col[v]) = make_float4(
-                        acc[4 * v] / maxv, acc[4 * v + 1] / maxv, acc[4 * v + 2] / maxv, acc[4 * v + 3] / maxv);
-            } else if (MODE == kModeRaw) {
-                float* o = out + q * N;
-#pragma unroll
-                for (int v = 0; v < VPL; ++v)
-                    *reinterpret_cast<float4*>(o + col[v]) =
-                        make_float4(acc[4 * v], acc[4 * v + 1], acc[4 * v + 2], acc[4 * v + 3]);
-#pragma unroll
-                for (int i = 0; i < NV; ++i) lmax = fmaxf(lmax, acc[i]);
-            } else if (MODE != kModeArgmax) {
-#pragma unroll
-                for (int i = 0; i < NV; ++i) lmax = fmaxf(lmax, acc[i]);
-            }
-        }
+        const bool ok = valid && CBN_OK_OR(q < Q && (long long)(l + 1) * VPL * 4 <= N, 3);
+        round_epilogue<VPL, MODE>(acc, col, l, L, valid, ok, q, N, out, maxv, lmax, true, fq, am);  // (wave-uniform call site)
         __builtin_amdgcn_wave_barrier();  // next round rewrites this wave's offsets
         if (first) CBN_STAMP(6);
         first = false;
     }
     CBN_STAMP(7);
-    if (MODE == kModeMax || MODE == kModeRaw) {
-        lmax = wave_max(lmax);
-        if (lane == 0) wmax[wid] = lmax;
-        __syncthreads();
-        if (tid == 0) {
-            float m = 0.f;
-            for (int i = 0; i < nthr / kWave; ++i) m = fmaxf(m, wmax[i]);
-            max_out[blockIdx.x] = __float_as_uint(m);  // one word per block, plain store
-        }
-        if (blockIdx.x == 0)  // words of blocks this launch does not have
-            for (int i = (int)gridDim.x + tid; i < n_max; i += nthr) max_out[i] = 0u;
-    }
+    if (MODE == kModeMax || MODE == kModeRaw) publish_block_max(lmax, wmax, max_out, n_max, lane, wid, tid, nthr);
     if (MODE == kModeFused) {
-        lmax = wave_max(lmax);
-        if (lane == 0) wmax[wid] = lmax;
-        __syncthreads();
-        if (wid == 0) {
-            const int nw = nthr / kWave;
-            const unsigned gm = slot_barrier_max(sync, epoch, wave_max(lane < nw ? wmax[lane] : 0.f));
-            if (lane == 0) {
-                wmax[0] = __uint_as_float(gm);
-                if (blockIdx.x == 0 && max_out) *max_out = gm;
-            }
-        }
-        CBN_STAMP(8);
-        __syncthreads();
-        CBN_STAMP(9);
-        maxv = wmax[0];
-        if (fq >= 0) {
-            float* o = out + fq * N;
-#pragma unroll
-            for (int v = 0; v < VPL; ++v)
-                *reinterpret_cast<float4*>(o + col[v]) = make_float4(
-                    acc[4 * v] / maxv, acc[4 * v + 1] / maxv, acc[4 * v + 2] / maxv, acc[4 * v + 3] / maxv);
-        }
+        maxv = fused_block_max(lmax, wmax, sync, epoch, max_out, lane, wid, nthr CBN_STAMP_ARG);
+        if (fq >= 0) store_row_div<VPL>(out + fq * N, col, acc, maxv);
         CBN_STAMP(10);
     }
 }
@@ -1257,13 +1310,7 @@ k_query_cols(int rec_off, int nf, int ns, const float* __restrict__ gimage, int 
     const QSlot* srec = reinterpret_cast<const QSlot*>(simg + lrec + nf * kRecFloats);
 
     float maxv = 1.f;
-    if (MODE == kModeWrite) {
-        unsigned m = 0;
-        for (int i = lane; i < n_max; i += kWave) m = max(m, max_in[i]);
-        m = wave_max_u(m);
-        maxv = __uint_as_float(m);
-        if (max_out && blockIdx.x == 0 && tid == 0) *max_out = m;
-    }
+    if (MODE == kModeWrite) maxv = batch_max(max_in, n_max, max_out, lane, tid);
     // the product loop's records, lane f <- factor f (nf <= 64, host-checked)
     int4 cra, crb;
     {
@@ -1399,28 +1446,7 @@ k_query_cols(int rec_off, int nf, int ns, const float* __restrict__ gimage, int 
 #pragma unroll
             for (int i = 0; i < NV; ++i) acc0[i] = acc[i];
         }
-        if (MODE == kModeArgmax) argmax_store<VPL>(acc, col, l, L, valid, q, am);  // (wave-uniform call site)
-        if (valid) {
-            if (MODE == kModeFused && !first) fq = q;
-            if (MODE == kModeWrite) {
-                float* o = out + q * N;
-#pragma unroll
-                for (int v = 0; v < VPL; ++v)
-                    *reinterpret_cast<float4*>(o + col[v]) = make_float4(
-                        acc[4 * v] / maxv, acc[4 * v + 1] / maxv, acc[4 * v + 2] / maxv, acc[4 * v + 3] / maxv);
-            } else if (MODE == kModeRaw) {
-                float* o = out + q * N;
-#pragma unroll
-                for (int v = 0; v < VPL; ++v)
-                    *reinterpret_cast<float4*>(o + col[v]) =
-                        make_float4(acc[4 * v], acc[4 * v + 1], acc[4 * v + 2], acc[4 * v + 3]);
-#pragma unroll
-                for (int i = 0; i < NV; ++i) lmax = fmaxf(lmax, acc[i]);
-            } else if (MODE != kModeArgmax) {
-#pragma unroll
-                for (int i = 0; i < NV; ++i) lmax = fmaxf(lmax, acc[i]);
-            }
-        }
+        round_epilogue<VPL, MODE>(acc, col, l, L, valid, valid, q, N, out, maxv, lmax, !first, fq, am);  // (wave-uniform call site)
         // the next round rewrites this query slot's indices (lanes of one wave)
         __builtin_amdgcn_s_waitcnt(0xC07F);
         __builtin_amdgcn_wave_barrier();
@@ -1428,48 +1454,11 @@ k_query_cols(int rec_off, int nf, int ns, const float* __restrict__ gimage, int 
         first = false;
     }
     CBN_STAMP(7);
-    if (MODE == kModeMax || MODE == kModeRaw) {
-        lmax = wave_max(lmax);
-        if (lane == 0) wmax[wid] = lmax;
-        __syncthreads();
-        if (tid == 0) {
-            float m = 0.f;
-            for (int i = 0; i < nthr / kWave; ++i) m = fmaxf(m, wmax[i]);
-            max_out[blockIdx.x] = __float_as_uint(m);
-        }
-        if (blockIdx.x == 0)
-            for (int i = (int)gridDim.x + tid; i < n_max; i += nthr) max_out[i] = 0u;
-    }
+    if (MODE == kModeMax || MODE == kModeRaw) publish_block_max(lmax, wmax, max_out, n_max, lane, wid, tid, nthr);
     if (MODE == kModeFused) {
-        lmax = wave_max(lmax);
-        if (lane == 0) wmax[wid] = lmax;
-        __syncthreads();
-        if (wid == 0) {
-            const int nw = nthr / kWave;
-            const unsigned gm = slot_barrier_max(sync, epoch, wave_max(lane < nw ? wmax[lane] : 0.f));
-            if (lane == 0) {
-                wmax[0] = __uint_as_float(gm);
-                if (blockIdx.x == 0 && max_out) *max_out = gm;
-            }
-        }
-        CBN_STAMP(8);
-        __syncthreads();
-        CBN_STAMP(9);
-        maxv = wmax[0];
-        if (fq0 >= 0) {
-            float* o = out + fq0 * N;
-#pragma unroll
-            for (int v = 0; v < VPL; ++v)
-                *reinterpret_cast<float4*>(o + col[v]) = make_float4(
-                    acc0[4 * v] / maxv, acc0[4 * v + 1] / maxv, acc0[4 * v + 2] / maxv, acc0[4 * v + 3] / maxv);
-        }
-        if (fq >= 0) {
-            float* o = out + fq * N;
-#pragma unroll
-            for (int v = 0; v < VPL; ++v)
-                *reinterpret_cast<float4*>(o + col[v]) = make_float4(
-                    acc[4 * v] / maxv, acc[4 * v + 1] / maxv, acc[4 * v + 2] / maxv, acc[4 * v + 3] / maxv);
-        }
+        maxv = fused_block_max(lmax, wmax, sync, epoch, max_out, lane, wid, nthr CBN_STAMP_ARG);
+        if (fq0 >= 0) store_row_div<VPL>(out + fq0 * N, col, acc0, maxv);
+        if (fq >= 0) store_row_div<VPL>(out + fq * N, col, acc, maxv);
         CBN_STAMP(10);
     }
 }
@@ -1547,13 +1536,7 @@ k_query_slots(int nf, int ns, const float* __restrict__ gimage, int qslot_off, c
     __syncthreads();
     CBN_STAMP(2);
     float maxv = 1.f;
-    if (MODE == kModeWrite) {
-        unsigned m = 0;
-        for (int i = lane; i < n_max; i += kWave) m = max(m, max_in[i]);
-        m = wave_max_u(m);
-        maxv = __uint_as_float(m);
-        if (max_out && blockIdx.x == 0 && tid == 0) *max_out = m;
-    }
+    if (MODE == kModeWrite) maxv = batch_max(max_in, n_max, max_out, lane, tid);
     float lmax = 0.f;
     const int ql = tid / L;  // this lane's query within the block round
     const int l = tid - ql * L;
@@ -1831,28 +1814,7 @@ k_query_slots(int nf, int ns, const float* __restrict__ gimage, int qslot_off, c
 #pragma unroll
             for (int i = 0; i < NV; ++i) acc0[i] = acc[i];
         }
-        if (MODE == kModeArgmax) argmax_store<VPL>(acc, col, l, L, valid, q, am);  // (wave-uniform call site)
-        if (valid) {
-            if (MODE == kModeFused && !first) fq = q;
-            if (MODE == kModeWrite) {
-                float* o = out + q * N;
-#pragma unroll
-                for (int v = 0; v < VPL; ++v)
-                    *reinterpret_cast<float4*>(o + col[v]) = make_float4(
-                        acc[4 * v] / maxv, acc[4 * v + 1] / maxv, acc[4 * v + 2] / maxv, acc[4 * v + 3] / maxv);
-            } else if (MODE == kModeRaw) {
-                float* o = out + q * N;
-#pragma unroll
-                for (int v = 0; v < VPL; ++v)
-                    *reinterpret_cast<float4*>(o + col[v]) =
-                        make_float4(acc[4 * v], acc[4 * v + 1], acc[4 * v + 2], acc[4 * v + 3]);
-#pragma unroll
-                for (int i = 0; i < NV; ++i) lmax = fmaxf(lmax, acc[i]);
-            } else if (MODE != kModeArgmax) {
-#pragma unroll
-                for (int i = 0; i < NV; ++i) lmax = fmaxf(lmax, acc[i]);
-            }
-        }
+        round_epilogue<VPL, MODE>(acc, col, l, L, valid, valid, q, N, out, maxv, lmax, !first, fq, am);  // (wave-uniform call site)
         // the next round rewrites this query slot's indices and offsets (lanes of one wave)
         __builtin_amdgcn_s_waitcnt(0xC07F);
         __builtin_amdgcn_wave_barrier();
@@ -1860,48 +1822,11 @@ k_query_slots(int nf, int ns, const float* __restrict__ gimage, int qslot_off, c
         first = false;
     }
     CBN_STAMP(7);
-    if (MODE == kModeMax || MODE == kModeRaw) {
-        lmax = wave_max(lmax);
-        if (lane == 0) wmax[wid] = lmax;
-        __syncthreads();
-        if (tid == 0) {
-            float m = 0.f;
-            for (int i = 0; i < nthr / kWave; ++i) m = fmaxf(m, wmax[i]);
-            max_out[blockIdx.x] = __float_as_uint(m);
-        }
-        if (blockIdx.x == 0)
-            for (int i = (int)gridDim.x + tid; i < n_max; i += nthr) max_out[i] = 0u;
-    }
+    if (MODE == kModeMax || MODE == kModeRaw) publish_block_max(lmax, wmax, max_out, n_max, lane, wid, tid, nthr);
     if (MODE == kModeFused) {
-        lmax = wave_max(lmax);
-        if (lane == 0) wmax[wid] = lmax;
-        __syncthreads();
-        if (wid == 0) {
-            const int nw = nthr / kWave;
-            const unsigned gm = slot_barrier_max(sync, epoch, wave_max(lane < nw ? wmax[lane] : 0.f));
-            if (lane == 0) {
-                wmax[0] = __uint_as_float(gm);
-                if (blockIdx.x == 0 && max_out) *max_out = gm;
-            }
-        }
-        CBN_STAMP(8);
-        __syncthreads();
-        CBN_STAMP(9);
-        maxv = wmax[0];
-        if (fq0 >= 0) {
-            float* o = out + fq0 * N;
-#pragma unroll
-            for (int v = 0; v < VPL; ++v)
-                *reinterpret_cast<float4*>(o + col[v]) = make_float4(
-                    acc0[4 * v] / maxv, acc0[4 * v + 1] / maxv, acc0[4 * v + 2] / maxv, acc0[4 * v + 3] / maxv);
-        }
-        if (fq >= 0) {
-            float* o = out + fq * N;
-#pragma unroll
-            for (int v = 0; v < VPL; ++v)
-                *reinterpret_cast<float4*>(o + col[v]) = make_float4(
-                    acc[4 * v] / maxv, acc[4 * v + 1] / maxv, acc[4 * v + 2] / maxv, acc[4 * v + 3] / maxv);
-        }
+        maxv = fused_block_max(lmax, wmax, sync, epoch, max_out, lane, wid, nthr CBN_STAMP_ARG);
+        if (fq0 >= 0) store_row_div<VPL>(out + fq0 * N, col, acc0, maxv);
+        if (fq >= 0) store_row_div<VPL>(out + fq * N, col, acc, maxv);
         CBN_STAMP(10);
     }
 }
@@ -2158,13 +2083,7 @@ k_query_staged(const float* __restrict__ gimage, int image_floats, int rec_off, 
     const int clo = (l + 4 * h0) * 4, chi = (l + 4 * (h0 ^ 1)) * 4;  // this lane's columns
     float lmax = 0.f;
     float maxv = 1.f;
-    if (MODE == kModeWrite) {
-        unsigned m = 0;
-        for (int i = lane; i < n_max; i += kWave) m = max(m, max_in[i]);
-        m = wave_max_u(m);
-        maxv = __uint_as_float(m);
-        if (max_out && blockIdx.x == 0 && tid == 0) *max_out = m;
-    }
+    if (MODE == kModeWrite) maxv = batch_max(max_in, n_max, max_out, lane, tid);
     float acc[8];
     long long fq = -1;
     int buf = 0;
@@ -2301,18 +2220,7 @@ k_query_staged(const float* __restrict__ gimage, int image_floats, int rec_off, 
                                 (float)((double)v.w * y));
         }
     }
-    if (MODE == kModeMax || MODE == kModeRaw) {
-        lmax = wave_max(lmax);
-        if (lane == 0) wmax[wid] = lmax;
-        __syncthreads();
-        if (tid == 0) {
-            float m = 0.f;
-            for (int i = 0; i < kQueryThreads / kWave; ++i) m = fmaxf(m, wmax[i]);
-            max_out[blockIdx.x] = __float_as_uint(m);  // one word per block, plain store
-        }
-        if (blockIdx.x == 0)  // words of blocks this launch does not have
-            for (int i = (int)gridDim.x + tid; i < n_max; i += kQueryThreads) max_out[i] = 0u;
-    }
+    if (MODE == kModeMax || MODE == kModeRaw) publish_block_max(lmax, wmax, max_out, n_max, lane, wid, tid, kQueryThreads);
     if (MODE == kModeFused) {
         // The two reductions in front of the publish by DPP: no LDS round trips
         // on the way into the barrier.  wave_max_nonneg orders floats by their
@@ -2685,37 +2593,14 @@ void allow_fast_lds(int bytes) {
                               hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
 }
 
-// WRITE=false: per-block maxima -> max_out[0, max_slots); WRITE=true: divide by
-// the max of max_in[0, n_max) (and publish it in *max_out when non-null)
-template <int VPL, bool LDS, bool WRITE>
-int launch_fast_v(cbn_plan* p, long long Q, const EvPtrs& ev, const unsigned* max_in, int n_max, unsigned* max_out,
-                  float* out, hipStream_t s) {
-    const int L = p->N / (4 * VPL);
-    const long long cap = p->max_slots;  // #CUs x blocks per CU, one max word each
-    long long blocks = (Q * L + kQueryThreads - 1) / kQueryThreads;
-    if (blocks > cap) blocks = cap;
-    if (!WRITE) n_max = p->max_slots;
-    launch_fast_k<VPL, LDS, WRITE ? kModeWrite : kModeMax>(p, (unsigned)blocks, s, ev, Q, L, 0u, max_in, n_max,
-                                                          max_out, out);
-    HIP_TRY(hipGetLastError());
-    return CBN_OK;
-}
-
-// Single-launch path: one round per wave, so Q <= blocks * 16 waves * (64 / L);
-// blocks <= #CUs with one block per CU, so every block is resident at once.
-template <int VPL, bool LDS>
-int launch_fused_v(cbn_plan* p, long long Q, const EvPtrs& ev, unsigned* max_bits, float* out, hipStream_t s) {
-    const int L = p->N / (4 * VPL);
-    const long long per_block = (long long)(kQueryThreads / kWave) * (kWave / L);
-    long long blocks = (Q + per_block - 1) / per_block;
-    // k_query_slots / k_query_cols: beyond one round per block, every CU's block takes two
-    // (fused_capacity allows Q <= 2 rounds of the co-resident grid)
-    if ((p->slots || p->cols) && CBN_SLOTS_FUSED2) blocks = std::min<long long>(blocks, std::min<long long>(num_cu(), kMaxSlots));
-    const unsigned epoch = ++p->fused_epoch;  // 1, 2, ... (0 = never published)
-    if (p->fused_epoch == 0xFFFFFFFFu) p->fused_epoch = 0;
-    launch_fast_k<VPL, LDS, kModeFused>(p, (unsigned)blocks, s, ev, Q, L, epoch, nullptr, 0, max_bits, out);
-    HIP_TRY(hipGetLastError());
-    return CBN_OK;
+// The plan's kernel variant as compile-time constants: f(VPL, LDS) with
+// std::integral_constant arguments, resolved from (p->vpl, p->use_lds) once.
+template <class F>
+auto with_variant(const cbn_plan* p, F&& f) {
+    using V1 = std::integral_constant<int, 1>;
+    using V2 = std::integral_constant<int, 2>;
+    if (p->use_lds) return p->vpl == 2 ? f(V2{}, std::true_type{}) : f(V1{}, std::true_type{});
+    return p->vpl == 2 ? f(V2{}, std::false_type{}) : f(V1{}, std::false_type{});
 }
 
 // CUs a raw launch leaves free (CBN_RAW_RESERVE_CU, diagnostic A/B knob): room
@@ -2730,52 +2615,113 @@ int raw_reserve_cu() {
     return v;
 }
 
-template <int VPL, bool LDS>
-int launch_raw_v(cbn_plan* p, long long Q, const EvPtrs& ev, unsigned* max_bits, float* out, hipStream_t s,
-                 const FoldJob* fold = nullptr) {
-    const int L = p->N / (4 * VPL);
-    const long long cap = std::max(1, p->max_slots - raw_reserve_cu());
-    long long blocks = (Q * L + kQueryThreads - 1) / kQueryThreads;
-    if (blocks > cap) blocks = cap;
-    launch_fast_k<VPL, LDS, kModeRaw>(p, (unsigned)blocks, s, ev, Q, L, 0u, nullptr, p->max_slots, max_bits, out,
-                                      fold);
+// Grid of a max / write / raw / arg-max launch: one block per 1024 (query,
+// lane) items, at most #CUs x blocks per CU (one max word each); raw and
+// arg-max launches leave raw_reserve_cu() of those free.
+unsigned query_blocks(const cbn_plan* p, long long Q, int L, bool reserve) {
+    const long long cap = reserve ? std::max(1, p->max_slots - raw_reserve_cu()) : p->max_slots;
+    return (unsigned)std::min((Q * L + kQueryThreads - 1) / kQueryThreads, cap);
+}
+
+// One max / write / raw / arg-max launch of the plan's fast-path kernel:
+//   kModeMax     per-block maxima -> max_out[0, max_slots)
+//   kModeWrite   out = products / max(max_in[0, n_max)), the max published in *max_out when non-null
+//   kModeRaw     unnormalised rows -> out, per-block maxima -> max_out[0, max_slots);
+//                `fold`: an earlier step's rows to scale on the way (staged plans)
+//   kModeArgmax  `am` only: the raw launch's grid and rounds, no rows, no max words
+template <int MODE>
+int launch_mode(cbn_plan* p, long long Q, const EvPtrs& ev, const unsigned* max_in, int n_max, unsigned* max_out,
+                float* out, hipStream_t s, const FoldJob* fold = nullptr, const ArgmaxOut* am = nullptr) {
+    if (MODE == kModeMax || MODE == kModeRaw) n_max = p->max_slots;
+    with_variant(p, [&](auto vpl, auto lds) {
+        const int L = p->N / (4 * vpl.value);
+        const unsigned blocks = query_blocks(p, Q, L, MODE == kModeRaw || MODE == kModeArgmax);
+        launch_fast_k<vpl.value, lds.value, MODE>(p, blocks, s, ev, Q, L, 0u, max_in, n_max, max_out, out, fold, am);
+    });
     HIP_TRY(hipGetLastError());
     return CBN_OK;
 }
 
-// The arg-max launch: the raw launch's grid and rounds, no rows, no max words.
-template <int VPL, bool LDS>
-int launch_argmax_v(cbn_plan* p, long long Q, const EvPtrs& ev, const ArgmaxOut& am, hipStream_t s) {
-    const int L = p->N / (4 * VPL);
-    const long long cap = std::max(1, p->max_slots - raw_reserve_cu());
-    long long blocks = (Q * L + kQueryThreads - 1) / kQueryThreads;
-    if (blocks > cap) blocks = cap;
-    launch_fast_k<VPL, LDS, kModeArgmax>(p, (unsigned)blocks, s, ev, Q, L, 0u, nullptr, 0, nullptr, nullptr, nullptr, &am);
+// Single-launch path: one round per wave, so Q <= blocks * 16 waves * (64 / L);
+// blocks <= #CUs with one block per CU, so every block is resident at once.
+int launch_fused(cbn_plan* p, long long Q, const EvPtrs& ev, unsigned* max_bits, float* out, hipStream_t s) {
+    const int L = p->N / (4 * p->vpl);
+    const long long per_block = (long long)(kQueryThreads / kWave) * (kWave / L);
+    long long blocks = (Q + per_block - 1) / per_block;
+    // k_query_slots / k_query_cols: beyond one round per block, every CU's block takes two
+    // (fused_capacity allows Q <= 2 rounds of the co-resident grid)
+    if ((p->slots || p->cols) && CBN_SLOTS_FUSED2) blocks = std::min<long long>(blocks, std::min<long long>(num_cu(), kMaxSlots));
+    const unsigned epoch = ++p->fused_epoch;  // 1, 2, ... (0 = never published)
+    if (p->fused_epoch == 0xFFFFFFFFu) p->fused_epoch = 0;
+    with_variant(p, [&](auto vpl, auto lds) {
+        launch_fast_k<vpl.value, lds.value, kModeFused>(p, (unsigned)blocks, s, ev, Q, L, epoch, nullptr, 0, max_bits, out);
+    });
     HIP_TRY(hipGetLastError());
     return CBN_OK;
 }
 
 // public pass API on the fast kernel: max pass -> per-block words -> one word
-template <int VEC, bool LDS, bool WRITE>
+template <bool WRITE>
 int launch_fast(cbn_plan* p, long long Q, const EvPtrs& ev, unsigned* max_bits, float* out, hipStream_t s) {
+    if (WRITE) return launch_mode<kModeWrite>(p, Q, ev, max_bits, 1, nullptr, out, s);
     unsigned* slots = p->d_sync + kMaxWordOff;
-    int rc;
-    if (WRITE)
-        rc = p->vpl == 2 ? launch_fast_v<2, LDS, true>(p, Q, ev, max_bits, 1, nullptr, out, s)
-                         : launch_fast_v<1, LDS, true>(p, Q, ev, max_bits, 1, nullptr, out, s);
-    else
-        rc = p->vpl == 2 ? launch_fast_v<2, LDS, false>(p, Q, ev, nullptr, 0, slots, nullptr, s)
-                         : launch_fast_v<1, LDS, false>(p, Q, ev, nullptr, 0, slots, nullptr, s);
-    if (rc || WRITE) return rc;
+    if (const int rc = launch_mode<kModeMax>(p, Q, ev, nullptr, 0, slots, nullptr, s)) return rc;
     hipLaunchKernelGGL(k_reduce_max, dim3(1), dim3(kWave), 0, s, slots, p->max_slots, max_bits);
     HIP_TRY(hipGetLastError());
     return CBN_OK;
 }
 
+// Evidence columns of one call -> EvPtrs: the plan's column count, and no null
+// column when there are queries to read it.
+int pack_evidence(const cbn_plan* p, const float* const* evidence, int n_ev, long long Q, EvPtrs& ev) {
+    if (n_ev != p->ns) return set_err(CBN_E_ARG, "plan expects %d evidence columns, got %d", p->ns, n_ev);
+    memset(&ev, 0, sizeof(ev));
+    for (int i = 0; i < n_ev; ++i) {
+        if (!evidence[i] && Q > 0) return set_err(CBN_E_ARG, "null evidence column %d", i);
+        ev.p[i] = evidence[i];
+    }
+    return CBN_OK;
+}
+
+// A fused launch whose grid barrier timed out flagged the plan's host-mapped
+// status word: the next call reports it, once.
+int take_pending_timeout(cbn_plan* p) {
+    if (!p->h_status || !__atomic_load_n(p->h_status, __ATOMIC_ACQUIRE)) return CBN_OK;
+    __atomic_store_n(p->h_status, 0u, __ATOMIC_RELEASE);
+    return set_err(CBN_E_TIMEOUT, "an earlier single-launch call of this plan timed out in its grid barrier "
+                                  "(not every block was resident); its rows are NaN");
+}
+
+// CBN_RUN_TIMED: the call's three events from the plan's ring (cbn_plan_timing
+// reads e[0] -> e[1] and e[1] -> e[2]).  begin() claims a slot and records
+// e[0]; an untimed call, or a full ring, records nothing.
+struct Timed {
+    hipEvent_t* e = nullptr;
+    hipStream_t s;
+    int begin(cbn_plan* p, int flags, hipStream_t stream) {
+        s = stream;
+        if (!(flags & CBN_RUN_TIMED) || p->ev_n >= cbn_plan::kRing) return CBN_OK;
+        hipEvent_t* slot = p->ev[p->ev_n];
+        for (int k = 0; k < 3; ++k)
+            if (!slot[k]) HIP_TRY(hipEventCreate(&slot[k]));
+        ++p->ev_n;
+        e = slot;
+        return mark(0);
+    }
+    int mark(int k) const {
+        if (e) HIP_TRY(hipEventRecord(e[k], s));
+        return CBN_OK;
+    }
+};
+#define CBN_TRY(expr)                           \
+    do {                                        \
+        if (const int _rc = (expr)) return _rc; \
+    } while (0)
+
 template <int VEC, bool LDS, bool WRITE>
 int launch_query(cbn_plan* p, long long Q, const EvPtrs& ev, unsigned* max_bits, float* out, hipStream_t s) {
     if (Q == 0) return CBN_OK;
-    if (p->fast) return launch_fast<VEC, LDS, WRITE>(p, Q, ev, max_bits, out, s);
+    if (p->fast) return launch_fast<WRITE>(p, Q, ev, max_bits, out, s);
     // every CU busy once there are >= 64 queries per block; a block walks its
     // contiguous range in LDS-sized chunks of CH queries
     const long long cap = (long long)num_cu() * p->blocks_per_cu;
@@ -2793,13 +2739,8 @@ int dispatch_query(cbn_plan* p, long long Q, const float* const* evidence, int n
                    float* out, hipStream_t s) {
     if (!p->d_fac || !p->d_slots || !p->d_image || !p->d_sync)
         return set_err(CBN_E_ARG, "plan has no device buffers");
-    if (n_ev != p->ns) return set_err(CBN_E_ARG, "plan expects %d evidence columns, got %d", p->ns, n_ev);
     EvPtrs ev;
-    memset(&ev, 0, sizeof(ev));
-    for (int i = 0; i < n_ev; ++i) {
-        if (!evidence[i] && Q > 0) return set_err(CBN_E_ARG, "null evidence column %d", i);
-        ev.p[i] = evidence[i];
-    }
+    CBN_TRY(pack_evidence(p, evidence, n_ev, Q, ev));
     if (p->vec == 4)
         return p->use_lds ? launch_query<4, true, WRITE>(p, Q, ev, max_bits, out, s)
                           : launch_query<4, false, WRITE>(p, Q, ev, max_bits, out, s);
@@ -2826,6 +2767,44 @@ void allow_lds(size_t bytes) {
 
 // the plan's arg-max runs in its query kernel (kModeArgmax): every fast-path table plan
 bool argmax_native(const cbn_plan* p) { return p->fast && !p->param && !p->direct; }
+
+// Rows of a factor's table: the product of its observed parents' cards
+// (clamped, so a sum over the factors cannot overflow).
+long long observed_rows(const cbn_factor_desc& h) {
+    long long rows = 1;
+    for (int p = 0; p < h.n_parents && p < kMaxP; ++p)
+        if (h.parent_ev_slot[p] >= 0 && h.parent_card[p] > 0) rows = std::min(rows * h.parent_card[p], 1LL << 40);
+    return rows;
+}
+
+// The product loops' records of k_query_cols / k_query_slots from the fast
+// path's: per observed parent (evidence slot << 24) | row weight in floats.
+// false (the kernel declines the plan): a slot's card beyond int16, a parent
+// whose card is not its slot's, a weight >= 2^24 or a slot >= 256.
+bool col_records(const std::vector<FastRec>& recs, const std::vector<int>& slot_card, int ns, int RS, bool all_lds,
+                 const unsigned long long (&lds_mask)[2], std::vector<ColRec>& cr) {
+    const int nf = (int)recs.size();
+    bool ok = true;
+    for (int sl = 0; sl < ns; ++sl) ok = ok && slot_card[sl] <= 32767;
+    for (int f = 0; f < nf && ok; ++f)
+        for (int q = 0; q < recs[f].n_obs; ++q)
+            ok = ok && (recs[f].card[q] & (kDenseBit - 1)) == slot_card[recs[f].slot[q]];
+    cr.resize(nf);
+    for (int f = 0; f < nf && ok; ++f) {
+        ColRec& c = cr[f];
+        memset(&c, 0, sizeof(c));
+        c.base = recs[f].table_off;
+        c.n_obs = recs[f].n_obs;
+        c.lds = all_lds || ((lds_mask[f >> 6] >> (f & 63)) & 1ull) ? 1 : 0;
+        long long w = RS;
+        for (int q = recs[f].n_obs - 1; q >= 0; --q) {
+            ok = ok && w < (1LL << 24) && recs[f].slot[q] < 256;
+            c.par[q] = (recs[f].slot[q] << 24) | (int)(w & 0xFFFFFF);
+            w *= recs[f].card[q] & (kDenseBit - 1);
+        }
+    }
+    return ok;
+}
 
 long long fused_capacity(const cbn_plan* p) {
     if (!p->fast || !p->fused_ok) return 0;
@@ -2937,13 +2916,7 @@ int cbn_plan_create(const cbn_factor_desc* factors, int32_t n_factors, int32_t n
     // an image that cannot fit LDS is read from L2/HBM, where the pad would make
     // every row straddle one more cache line: unpadded rows, 128-B aligned tables.
     long long total_rows = 0;
-    for (int f = 0; f < n_factors; ++f) {
-        long long rows = 1;
-        for (int p = 0; p < factors[f].n_parents && p < kMaxP; ++p)
-            if (factors[f].parent_ev_slot[p] >= 0 && factors[f].parent_card[p] > 0)
-                rows = std::min(rows * factors[f].parent_card[p], 1LL << 40);
-        total_rows += rows;
-    }
+    for (int f = 0; f < n_factors; ++f) total_rows += observed_rows(factors[f]);
     const bool global_tables = vec == 4 && total_rows * (N + 4) * 4 > (long long)kLdsBudget;
     // Paired layout (N = 32, tables in LDS, 8 columns per lane): factor f's rows
     // sit in bank half (f & 1) of 256-B super-rows -- even factors in banks 0-31,
@@ -2955,27 +2928,14 @@ int cbn_plan_create(const cbn_factor_desc* factors, int32_t n_factors, int32_t n
     long long class_rows[2] = {0, 0};
     int want_vpl = 2;
     if (const char* e = diag_env("CBN_FAST_VPL")) want_vpl = atoi(e);
-    for (int f = 0; f < n_factors; ++f) {
-        long long rows = 1;
-        for (int p = 0; p < factors[f].n_parents && p < kMaxP; ++p)
-            if (factors[f].parent_ev_slot[p] >= 0 && factors[f].parent_card[p] > 0)
-                rows = std::min(rows * factors[f].parent_card[p], 1LL << 40);
-        class_rows[f & 1] += rows;
-    }
+    for (int f = 0; f < n_factors; ++f) class_rows[f & 1] += observed_rows(factors[f]);
     bool paired = vec == 4 && N == 32 && !global_tables && want_vpl >= 2 && !diag_env("CBN_NO_PAIRED") &&
                   std::max(class_rows[0], class_rows[1]) * 64 * 4 <= (long long)kLdsBudget * 3 / 4;
     // leading 1-row factors (roots / unobserved-parent factors) fold into the
     // first multi-row factor (k_merge_prefix); the staged kernel skips them
     int prefix = 0;
     if (paired && !diag_env("CBN_NO_PREFIX")) {
-        while (prefix < n_factors - 1 && prefix < 8) {
-            long long rows = 1;
-            for (int p = 0; p < factors[prefix].n_parents && p < kMaxP; ++p)
-                if (factors[prefix].parent_ev_slot[p] >= 0 && factors[prefix].parent_card[p] > 0)
-                    rows *= factors[prefix].parent_card[p];
-            if (rows != 1) break;
-            ++prefix;
-        }
+        while (prefix < n_factors - 1 && prefix < 8 && observed_rows(factors[prefix]) == 1) ++prefix;
     }
     const int RS = paired ? 64 : vec == 4 && !global_tables ? N + 4 : N;
     const long long talign = global_tables ? 32 : 4;
@@ -3016,13 +2976,8 @@ int cbn_plan_create(const cbn_factor_desc* factors, int32_t n_factors, int32_t n
             if (2 * (side + recb) <= (long long)kLdsBudget)
                 budget = std::min(budget, (long long)kLdsBudget / 2 - side - recb - 1024);
             std::vector<std::pair<long long, int>> by_size;
-            for (int f = 0; f < n_factors; ++f) {
-                long long rows = 1;
-                for (int q = 0; q < factors[f].n_parents && q < kMaxP; ++q)
-                    if (factors[f].parent_ev_slot[q] >= 0 && factors[f].parent_card[q] > 0)
-                        rows = std::min(rows * factors[f].parent_card[q], 1LL << 40);
-                by_size.push_back({(rows * RS + talign - 1) & ~(talign - 1), f});
-            }
+            for (int f = 0; f < n_factors; ++f)
+                by_size.push_back({(observed_rows(factors[f]) * RS + talign - 1) & ~(talign - 1), f});
             std::stable_sort(by_size.begin(), by_size.end());
             for (const auto& [tf, f] : by_size) {
                 if ((lds_tab_end + tf) * 4 > budget) break;  // floats vs bytes
@@ -3291,32 +3246,14 @@ int cbn_plan_create(const cbn_factor_desc* factors, int32_t n_factors, int32_t n
             // ran 459 -> 534 us at 262 144 queries (profiles/r04_cols_ab.json)
             if (!P->staged && !P->paired && Lf <= 2 && ns <= kFastPtrsSmall && n_factors <= kWave &&
                 !diag_env("CBN_NO_COLS")) {
-                bool ok_c = true;
-                for (int sl = 0; sl < ns; ++sl) ok_c = ok_c && slot_card[sl] <= 32767;
-                for (int f = 0; f < n_factors && ok_c; ++f)
-                    for (int q = 0; q < recs[f].n_obs; ++q)
-                        ok_c = ok_c && (recs[f].card[q] & (kDenseBit - 1)) == slot_card[recs[f].slot[q]];
+                std::vector<ColRec> cr;
+                bool ok_c = col_records(recs, slot_card, ns, RS, P->use_lds, lds_mask, cr);
                 const size_t QBc = (size_t)kQueryThreads / Lf;
                 const size_t cols_bytes =
                     ((P->use_lds ? img_bytes
                                  : (size_t)P->lds_tab_floats * 4 + ((size_t)n_factors * kRecFloats + (size_t)ns * 4) * 4) +
                      (size_t)((ns + 1) & ~1) * sizeof(void*) + (((size_t)ns * QBc + 1) & ~size_t(1)) * 2 +
                      (kQueryThreads / kWave) * 4 + 64 + 16 + (size_t)N * 4 + 15) & ~size_t(15);  // (+ zero row)
-                // the product loop's scalar records: (slot << 24) | row weight, weights < 2^24
-                std::vector<ColRec> cr(n_factors);
-                for (int f = 0; f < n_factors && ok_c; ++f) {
-                    ColRec& c = cr[f];
-                    memset(&c, 0, sizeof(c));
-                    c.base = recs[f].table_off;
-                    c.n_obs = recs[f].n_obs;
-                    c.lds = P->use_lds || ((lds_mask[f >> 6] >> (f & 63)) & 1ull) ? 1 : 0;
-                    long long w = RS;
-                    for (int q = recs[f].n_obs - 1; q >= 0; --q) {
-                        ok_c = ok_c && w < (1LL << 24) && recs[f].slot[q] < 256;
-                        c.par[q] = (recs[f].slot[q] << 24) | (int)(w & 0xFFFFFF);
-                        w *= recs[f].card[q] & (kDenseBit - 1);
-                    }
-                }
                 if (ok_c && cols_bytes <= (size_t)kLdsBudget) {
                     ok_c = hipMalloc(&P->d_crec, sizeof(ColRec) * n_factors) == hipSuccess &&
                            hipMemcpy(P->d_crec, cr.data(), sizeof(ColRec) * n_factors, hipMemcpyHostToDevice) ==
@@ -3334,27 +3271,11 @@ int cbn_plan_create(const cbn_factor_desc* factors, int32_t n_factors, int32_t n
             // loaded once per query instead of kFastObs loads per factor
             if (!P->staged && !P->paired && !P->cols && !P->use_lds && Lf > 2 && ns <= kFastPtrsSmall &&
                 n_factors <= 128 && !diag_env("CBN_NO_SLOTS")) {
-                bool ok_s = true;
-                for (int sl = 0; sl < ns; ++sl) ok_s = ok_s && slot_card[sl] <= 32767;
-                for (int f = 0; f < n_factors && ok_s; ++f)
-                    for (int q = 0; q < recs[f].n_obs; ++q)
-                        ok_s = ok_s && (recs[f].card[q] & (kDenseBit - 1)) == slot_card[recs[f].slot[q]];
-                std::vector<ColRec> cr(n_factors);
-                for (int f = 0; f < n_factors && ok_s; ++f) {
-                    ColRec& c = cr[f];
-                    memset(&c, 0, sizeof(c));
-                    c.base = recs[f].table_off;
-                    c.n_obs = recs[f].n_obs;
-                    c.lds = ((lds_mask[f >> 6] >> (f & 63)) & 1ull) ? 1 : 0;
-                    long long w = RS;
-                    for (int q = recs[f].n_obs - 1; q >= 0; --q) {
-                        ok_s = ok_s && w < (1LL << 24) && recs[f].slot[q] < 256;
-                        c.par[q] = (recs[f].slot[q] << 24) | (int)(w & 0xFFFFFF);
-                        w *= recs[f].card[q] & (kDenseBit - 1);
-                    }
-                    // the offset (table base + row x RS) must fit an int
-                    ok_s = ok_s && (long long)recs[f].table_off + w < (1LL << 31);
-                }
+                std::vector<ColRec> cr;
+                bool ok_s = col_records(recs, slot_card, ns, RS, false, lds_mask, cr);
+                // the offset (table base + row x RS) must fit an int
+                for (int f = 0; f < n_factors; ++f)
+                    ok_s = ok_s && (long long)recs[f].table_off + (long long)fac[f].rows * RS < (1LL << 31);
                 const size_t sb = slots_lds_bytes(P->lds_tab_floats, ns, n_factors, kQueryThreads / Lf);
                 if (ok_s && sb <= (size_t)kLdsBudget) {
                     if (hipMalloc(&P->d_crec, sizeof(ColRec) * n_factors) != hipSuccess ||
@@ -3387,13 +3308,11 @@ int cbn_plan_create(const cbn_factor_desc* factors, int32_t n_factors, int32_t n
                 allow_fast_lds<2, false, kModeFused>(kLdsBudget);
                 int nb = 0;
                 const int spl = (ns + Lf - 1) / Lf;  // k_query_cols: slots per lane
-                const void* fn = P->staged ? reinterpret_cast<const void*>(&k_query_staged<kModeFused>)
-                                 : P->slots ? (vpl == 2 ? reinterpret_cast<const void*>(&k_query_slots<2, kModeFused>)
-                                                        : reinterpret_cast<const void*>(&k_query_slots<1, kModeFused>))
-                                 : P->use_lds ? (vpl == 2 ? fast_kernel_fn<2, true, kModeFused>(n_factors, P->cols, spl)
-                                                          : fast_kernel_fn<1, true, kModeFused>(n_factors, P->cols, spl))
-                                              : (vpl == 2 ? fast_kernel_fn<2, false, kModeFused>(n_factors, P->cols, spl)
-                                                          : fast_kernel_fn<1, false, kModeFused>(n_factors, P->cols, spl));
+                const void* fn = with_variant(P, [&](auto v, auto lds) {
+                    if (P->staged) return reinterpret_cast<const void*>(&k_query_staged<kModeFused>);
+                    if (P->slots) return reinterpret_cast<const void*>(&k_query_slots<v.value, kModeFused>);
+                    return fast_kernel_fn<v.value, lds.value, kModeFused>(n_factors, P->cols, spl);
+                });
                 const size_t lb = P->staged ? P->staged_lds_bytes : P->fast_lds_bytes;
                 if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, kQueryThreads, lb) == hipSuccess && nb >= 1)
                     P->fused_ok = true;
@@ -3491,147 +3410,66 @@ int cbn_plan_query_write(cbn_plan* plan, int64_t n_queries, const float* const* 
 int cbn_plan_run(cbn_plan* plan, int64_t n_queries, const float* const* evidence, int32_t n_evidence,
                  uint32_t* max_bits, float* out, int32_t flags, void* stream) {
     if (!plan) return set_err(CBN_E_ARG, "null plan");
-    if (plan->h_status && __atomic_load_n(plan->h_status, __ATOMIC_ACQUIRE)) {
-        __atomic_store_n(plan->h_status, 0u, __ATOMIC_RELEASE);
-        return set_err(CBN_E_TIMEOUT, "an earlier single-launch call of this plan timed out in its grid barrier "
-                                      "(not every block was resident); its rows are NaN");
-    }
+    CBN_TRY(take_pending_timeout(plan));
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    int rc;
     if (plan->direct) return direct_run(plan, n_queries, evidence, n_evidence, max_bits, out, flags, s);
+    Timed t;
     if (plan->param) {
-        hipEvent_t* e = nullptr;
-        if ((flags & CBN_RUN_TIMED) && plan->ev_n < cbn_plan::kRing) {
-            e = plan->ev[plan->ev_n];
-            for (int k = 0; k < 3; ++k)
-                if (!e[k]) HIP_TRY(hipEventCreate(&e[k]));
-            ++plan->ev_n;
-            HIP_TRY(hipEventRecord(e[0], s));
-            HIP_TRY(hipEventRecord(e[1], s));
-        }
-        rc = param_run(plan, n_queries, evidence, n_evidence, max_bits, out, flags, s);
-        if (rc) return rc;
-        if (e) HIP_TRY(hipEventRecord(e[2], s));
-        return CBN_OK;
+        CBN_TRY(t.begin(plan, flags, s));
+        CBN_TRY(t.mark(1));
+        CBN_TRY(param_run(plan, n_queries, evidence, n_evidence, max_bits, out, flags, s));
+        return t.mark(2);
     }
-    if (flags & CBN_RUN_BUILD_TABLES) {
-        rc = cbn_plan_build_tables(plan, stream);
-        if (rc) return rc;
-    }
-    hipEvent_t* e = nullptr;
-    if ((flags & CBN_RUN_TIMED) && plan->ev_n < cbn_plan::kRing) {
-        e = plan->ev[plan->ev_n];
-        for (int k = 0; k < 3; ++k)
-            if (!e[k]) HIP_TRY(hipEventCreate(&e[k]));
-        ++plan->ev_n;
-        HIP_TRY(hipEventRecord(e[0], s));
-    }
+    if (flags & CBN_RUN_BUILD_TABLES) CBN_TRY(cbn_plan_build_tables(plan, stream));
+    CBN_TRY(t.begin(plan, flags, s));
+    const bool one_pass = n_queries > 0 && !(flags & CBN_RUN_TWO_PASS);
+    unsigned* words = plan->d_sync ? plan->d_sync + kMaxWordOff : nullptr;  // the plan's per-block max words
+    EvPtrs ev;
     if (flags & CBN_RUN_RAW) {
         if (!plan->fast) return set_err(CBN_E_UNSUPPORTED, "cbn_plan_run: raw launch needs a fast-path plan");
-        if (n_evidence != plan->ns) return set_err(CBN_E_ARG, "plan expects %d evidence columns, got %d", plan->ns, n_evidence);
+        CBN_TRY(pack_evidence(plan, evidence, n_evidence, n_queries, ev));
         if (!out || !max_bits) return set_err(CBN_E_ARG, "cbn_plan_run: null output");
         if (!plan->d_image || !plan->d_sync) return set_err(CBN_E_ARG, "plan has no device buffers");
         if (n_queries <= 0) return set_err(CBN_E_ARG, "cbn_plan_run: raw launch needs >= 1 query");
-        EvPtrs ev;
-        memset(&ev, 0, sizeof(ev));
-        for (int i = 0; i < n_evidence; ++i) {
-            if (!evidence[i]) return set_err(CBN_E_ARG, "null evidence column %d", i);
-            ev.p[i] = evidence[i];
-        }
-        if (e) HIP_TRY(hipEventRecord(e[1], s));
-        if (plan->use_lds)
-            rc = plan->vpl == 2 ? launch_raw_v<2, true>(plan, n_queries, ev, max_bits, out, s)
-                                : launch_raw_v<1, true>(plan, n_queries, ev, max_bits, out, s);
-        else
-            rc = plan->vpl == 2 ? launch_raw_v<2, false>(plan, n_queries, ev, max_bits, out, s)
-                                : launch_raw_v<1, false>(plan, n_queries, ev, max_bits, out, s);
-        if (rc) return rc;
-        if (e) HIP_TRY(hipEventRecord(e[2], s));
-        return CBN_OK;
+        CBN_TRY(t.mark(1));
+        CBN_TRY(launch_mode<kModeRaw>(plan, n_queries, ev, nullptr, 0, max_bits, out, s));
+        return t.mark(2);
     }
-    if (n_queries > 0 && !(flags & CBN_RUN_TWO_PASS) && fused_capacity(plan) >= n_queries) {
+    if (one_pass && fused_capacity(plan) >= n_queries) {
         // one launch: both passes with the products held in registers across a grid barrier
-        if (n_evidence != plan->ns) return set_err(CBN_E_ARG, "plan expects %d evidence columns, got %d", plan->ns, n_evidence);
+        CBN_TRY(pack_evidence(plan, evidence, n_evidence, n_queries, ev));
         if (!out || !max_bits) return set_err(CBN_E_ARG, "cbn_plan_run: null output");
-        EvPtrs ev;
-        memset(&ev, 0, sizeof(ev));
-        for (int i = 0; i < n_evidence; ++i) ev.p[i] = evidence[i];
-        if (e) HIP_TRY(hipEventRecord(e[1], s));
-        if (plan->use_lds)
-            rc = plan->vpl == 2 ? launch_fused_v<2, true>(plan, n_queries, ev, max_bits, out, s)
-                                : launch_fused_v<1, true>(plan, n_queries, ev, max_bits, out, s);
-        else
-            rc = plan->vpl == 2 ? launch_fused_v<2, false>(plan, n_queries, ev, max_bits, out, s)
-                                : launch_fused_v<1, false>(plan, n_queries, ev, max_bits, out, s);
-        if (rc) return rc;
-        if (e) HIP_TRY(hipEventRecord(e[2], s));
-        return CBN_OK;
+        CBN_TRY(t.mark(1));
+        CBN_TRY(launch_fused(plan, n_queries, ev, max_bits, out, s));
+        return t.mark(2);
     }
-    if (plan->fast && n_queries > 0 && !(flags & CBN_RUN_TWO_PASS) && reinterpret_cast<uintptr_t>(out) % 16 == 0) {
+    if (plan->fast && one_pass && reinterpret_cast<uintptr_t>(out) % 16 == 0) {
         // beyond the single launch: ONE compute pass (raw: unnormalised rows +
         // per-block maxima) and an HBM-bound in-place scale that reduces the
         // words, divides and publishes the max in *max_bits -- instead of
         // computing every product twice (max pass + write pass)
-        if (n_evidence != plan->ns) return set_err(CBN_E_ARG, "plan expects %d evidence columns, got %d", plan->ns, n_evidence);
+        CBN_TRY(pack_evidence(plan, evidence, n_evidence, n_queries, ev));
         if (!max_bits) return set_err(CBN_E_ARG, "cbn_plan_run: null output");
-        EvPtrs ev;
-        memset(&ev, 0, sizeof(ev));
-        for (int i = 0; i < n_evidence; ++i) {
-            if (!evidence[i]) return set_err(CBN_E_ARG, "null evidence column %d", i);
-            ev.p[i] = evidence[i];
-        }
-        unsigned* words = plan->d_sync + kMaxWordOff;
-        if (plan->use_lds)
-            rc = plan->vpl == 2 ? launch_raw_v<2, true>(plan, n_queries, ev, words, out, s)
-                                : launch_raw_v<1, true>(plan, n_queries, ev, words, out, s);
-        else
-            rc = plan->vpl == 2 ? launch_raw_v<2, false>(plan, n_queries, ev, words, out, s)
-                                : launch_raw_v<1, false>(plan, n_queries, ev, words, out, s);
-        if (rc) return rc;
-        if (e) HIP_TRY(hipEventRecord(e[1], s));
-        rc = launch_scale(out, n_queries * (long long)plan->N, words, plan->max_slots, max_bits, s);
-        if (rc) return rc;
-        if (e) HIP_TRY(hipEventRecord(e[2], s));
-        return CBN_OK;
+        CBN_TRY(launch_mode<kModeRaw>(plan, n_queries, ev, nullptr, 0, words, out, s));
+        CBN_TRY(t.mark(1));
+        CBN_TRY(launch_scale(out, n_queries * (long long)plan->N, words, plan->max_slots, max_bits, s));
+        return t.mark(2);
     }
     if (plan->fast && n_queries > 0) {
         // two launches: per-block maxima into the plan's words, then the write
         // pass reduces them itself and publishes the max in *max_bits
-        if (n_evidence != plan->ns) return set_err(CBN_E_ARG, "plan expects %d evidence columns, got %d", plan->ns, n_evidence);
+        CBN_TRY(pack_evidence(plan, evidence, n_evidence, n_queries, ev));
         if (!out || !max_bits) return set_err(CBN_E_ARG, "cbn_plan_run: null output");
-        EvPtrs ev;
-        memset(&ev, 0, sizeof(ev));
-        for (int i = 0; i < n_evidence; ++i) {
-            if (!evidence[i]) return set_err(CBN_E_ARG, "null evidence column %d", i);
-            ev.p[i] = evidence[i];
-        }
-        unsigned* words = plan->d_sync + kMaxWordOff;
-        const bool lds = plan->use_lds;
-        if (plan->vpl == 2)
-            rc = lds ? launch_fast_v<2, true, false>(plan, n_queries, ev, nullptr, 0, words, nullptr, s)
-                     : launch_fast_v<2, false, false>(plan, n_queries, ev, nullptr, 0, words, nullptr, s);
-        else
-            rc = lds ? launch_fast_v<1, true, false>(plan, n_queries, ev, nullptr, 0, words, nullptr, s)
-                     : launch_fast_v<1, false, false>(plan, n_queries, ev, nullptr, 0, words, nullptr, s);
-        if (rc) return rc;
-        if (e) HIP_TRY(hipEventRecord(e[1], s));
-        if (plan->vpl == 2)
-            rc = lds ? launch_fast_v<2, true, true>(plan, n_queries, ev, words, plan->max_slots, max_bits, out, s)
-                     : launch_fast_v<2, false, true>(plan, n_queries, ev, words, plan->max_slots, max_bits, out, s);
-        else
-            rc = lds ? launch_fast_v<1, true, true>(plan, n_queries, ev, words, plan->max_slots, max_bits, out, s)
-                     : launch_fast_v<1, false, true>(plan, n_queries, ev, words, plan->max_slots, max_bits, out, s);
-        if (rc) return rc;
-        if (e) HIP_TRY(hipEventRecord(e[2], s));
-        return CBN_OK;
+        CBN_TRY(launch_mode<kModeMax>(plan, n_queries, ev, nullptr, 0, words, nullptr, s));
+        CBN_TRY(t.mark(1));
+        CBN_TRY(launch_mode<kModeWrite>(plan, n_queries, ev, words, plan->max_slots, max_bits, out, s));
+        return t.mark(2);
     }
-    rc = cbn_plan_query_max(plan, n_queries, evidence, n_evidence, max_bits, stream);
-    if (rc) return rc;
-    if (e) HIP_TRY(hipEventRecord(e[1], s));
-    rc = cbn_plan_query_write(plan, n_queries, evidence, n_evidence, max_bits, out, stream);
-    if (rc) return rc;
-    if (e) HIP_TRY(hipEventRecord(e[2], s));
-    return CBN_OK;
+    // generic plans (and empty batches): the public max and write passes
+    CBN_TRY(cbn_plan_query_max(plan, n_queries, evidence, n_evidence, max_bits, stream));
+    CBN_TRY(t.mark(1));
+    CBN_TRY(cbn_plan_query_write(plan, n_queries, evidence, n_evidence, max_bits, out, stream));
+    return t.mark(2);
 }
 
 int cbn_plan_run_fold(cbn_plan* plan, int64_t n_queries, const float* const* evidence, int32_t n_evidence,
@@ -3646,46 +3484,24 @@ int cbn_plan_run_fold(cbn_plan* plan, int64_t n_queries, const float* const* evi
         fold_n_words > kFoldW * kWave)
         return set_err(CBN_E_ARG, "cbn_plan_run_fold: fold rows must be 16-B aligned float4s, 1..%d words",
                        kFoldW * kWave);
-    if (plan->h_status && __atomic_load_n(plan->h_status, __ATOMIC_ACQUIRE)) {
-        __atomic_store_n(plan->h_status, 0u, __ATOMIC_RELEASE);
-        return set_err(CBN_E_TIMEOUT, "an earlier single-launch call of this plan timed out in its grid barrier "
-                                      "(not every block was resident); its rows are NaN");
-    }
+    CBN_TRY(take_pending_timeout(plan));
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    int rc;
-    if (flags & CBN_RUN_BUILD_TABLES) {
-        rc = cbn_plan_build_tables(plan, stream);
-        if (rc) return rc;
-    }
-    if (n_evidence != plan->ns) return set_err(CBN_E_ARG, "plan expects %d evidence columns, got %d", plan->ns, n_evidence);
+    if (flags & CBN_RUN_BUILD_TABLES) CBN_TRY(cbn_plan_build_tables(plan, stream));
+    EvPtrs ev;
+    CBN_TRY(pack_evidence(plan, evidence, n_evidence, n_queries, ev));
     if (!out || !max_bits) return set_err(CBN_E_ARG, "cbn_plan_run_fold: null output");
     if (n_queries <= 0) return set_err(CBN_E_ARG, "cbn_plan_run_fold: raw launch needs >= 1 query");
-    EvPtrs ev;
-    memset(&ev, 0, sizeof(ev));
-    for (int i = 0; i < n_evidence; ++i) {
-        if (!evidence[i]) return set_err(CBN_E_ARG, "null evidence column %d", i);
-        ev.p[i] = evidence[i];
-    }
-    hipEvent_t* e = nullptr;
-    if ((flags & CBN_RUN_TIMED) && plan->ev_n < cbn_plan::kRing) {
-        e = plan->ev[plan->ev_n];
-        for (int k = 0; k < 3; ++k)
-            if (!e[k]) HIP_TRY(hipEventCreate(&e[k]));
-        ++plan->ev_n;
-        HIP_TRY(hipEventRecord(e[0], s));
-        HIP_TRY(hipEventRecord(e[1], s));
-    }
+    Timed t;
+    CBN_TRY(t.begin(plan, flags, s));
+    CBN_TRY(t.mark(1));
     FoldJob fj;
     memset(&fj, 0, sizeof(fj));
     fj.rows = fold_rows;
     fj.words = fold_words;
     fj.n4 = fold_n_elems / 4;
     fj.n_words = fold_n_words;
-    rc = plan->vpl == 2 ? launch_raw_v<2, true>(plan, n_queries, ev, max_bits, out, s, &fj)
-                        : launch_raw_v<1, true>(plan, n_queries, ev, max_bits, out, s, &fj);
-    if (rc) return rc;
-    if (e) HIP_TRY(hipEventRecord(e[2], s));
-    return CBN_OK;
+    CBN_TRY(launch_mode<kModeRaw>(plan, n_queries, ev, nullptr, 0, max_bits, out, s, &fj));
+    return t.mark(2);
 }
 
 int cbn_row_argmax(const float* rows, int64_t n_rows, int32_t n_cols, const float* target_values, int32_t* index,
@@ -3720,11 +3536,7 @@ int cbn_plan_run_argmax(cbn_plan* plan, int64_t n_queries, const float* const* e
         if (!plan->d_fac || !plan->d_slots || !plan->d_image || !plan->d_sync)
             return set_err(CBN_E_ARG, "plan has no device buffers");
     }
-    if (plan->h_status && __atomic_load_n(plan->h_status, __ATOMIC_ACQUIRE)) {
-        __atomic_store_n(plan->h_status, 0u, __ATOMIC_RELEASE);
-        return set_err(CBN_E_TIMEOUT, "an earlier single-launch call of this plan timed out in its grid barrier "
-                                      "(not every block was resident); its rows are NaN");
-    }
+    CBN_TRY(take_pending_timeout(plan));
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const ArgmaxOut am = {target_values, index, value, row_max};
     int rc;
@@ -3746,13 +3558,8 @@ int cbn_plan_run_argmax(cbn_plan* plan, int64_t n_queries, const float* const* e
         return launch_row_argmax(scratch, (long long)n_queries, plan->N, am, s);
     }
     EvPtrs ev;
-    memset(&ev, 0, sizeof(ev));
-    for (int i = 0; i < n_evidence; ++i) ev.p[i] = evidence[i];
-    if (plan->use_lds)
-        return plan->vpl == 2 ? launch_argmax_v<2, true>(plan, n_queries, ev, am, s)
-                              : launch_argmax_v<1, true>(plan, n_queries, ev, am, s);
-    return plan->vpl == 2 ? launch_argmax_v<2, false>(plan, n_queries, ev, am, s)
-                          : launch_argmax_v<1, false>(plan, n_queries, ev, am, s);
+    CBN_TRY(pack_evidence(plan, evidence, n_evidence, n_queries, ev));
+    return launch_mode<kModeArgmax>(plan, n_queries, ev, nullptr, 0, nullptr, nullptr, s, nullptr, &am);
 }
 
 int cbn_plan_status(cbn_plan* plan, int32_t* status) {

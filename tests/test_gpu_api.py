@@ -121,6 +121,34 @@ def test_out_argument_is_validated(gpu):
             bn.engine.infer("X5", ev, 4, out=bad)
 
 
+def test_null_evidence_column_is_rejected_on_the_single_launch_path(gpu):
+    """cbn_plan_run on a fused-eligible plan with a null evidence column (the
+    engine never passes one: a direct native call) returns CBN_E_ARG with the
+    message of the other paths, before any launch: ``out`` and the max word
+    keep their contents, and the plan still serves the next call."""
+    data, cols, edges = chain_data(6, 4, 3000, 5, stay=0.8)
+    bn = make_bn(BayesianNetwork, edges, cols, data, device=gpu)
+    ev = _t(sample_evidence(data, cols, ["X4"], 100, 3), gpu)
+    a, _ = bn.infer("X5", ev, N_max=4)
+    a = a.clone()
+    plan = next(iter(bn.engine._plans.values()))
+    lib = _native.load()
+    assert lib.cbn_plan_flags(plan.handle) & _native.CBN_PLAN_FUSED
+    assert lib.cbn_plan_fused_capacity(plan.handle) >= 100  # flags 0: the single-launch arm
+    out = torch.full((100, 4), -7.0, device=gpu)
+    word = torch.full((1,), 12345, dtype=torch.int32, device=gpu)
+    ptrs = (ctypes.c_void_p * 1)(None)
+    with torch.cuda.device(gpu):
+        rc = lib.cbn_plan_run(plan.handle, 100, ptrs, 1, word.data_ptr(), _native.ptr(out), 0,
+                              _native.stream_ptr(torch.device(gpu)))
+    assert rc == _native.CBN_E_ARG
+    assert lib.cbn_last_error().decode() == "null evidence column 0"
+    torch.cuda.synchronize()
+    assert (out == -7.0).all() and int(word.item()) == 12345  # nothing was launched
+    b, _ = bn.infer("X5", ev, N_max=4)
+    np.testing.assert_array_equal(b.cpu().numpy(), a.cpu().numpy())
+
+
 @pytest.mark.parametrize("every", [1, 3])
 def test_stepper_gather_one_rank(every, gpu):
     """The reassembly path of the stepper over a one-rank RCCL communicator:
