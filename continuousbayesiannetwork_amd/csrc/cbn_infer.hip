@@ -377,9 +377,38 @@ __device__ __forceinline__ int4 sload_int4(const void* p) {
 }
 
 // Copy n4 float4 from global to LDS with LDS-DMA (global_load_lds_dwordx4: no
-// VGPR staging; one wave-instruction moves 1 KiB).  Chunk order is rotated by
-// block so the CUs do not all hit the same L2 channel at once.  Completion is
+// VGPR staging; one wave-instruction moves one 1 KiB chunk).  Completion is
 // awaited by the caller's __syncthreads() (it waits vmcnt(0)).
+//
+// Each of the nw waves takes a contiguous run of chunks.  The runs are rotated
+// by block -- chunk (r + blockIdx % nchunk) % nchunk is the r-th one issued --
+// so the CUs do not all hit the same L2 channel at once; the rotation is
+// worked out once per wave and a run is walked as two wrap-free segments.
+// Inside a segment the stream is straight-line: groups of four chunks share
+// one address and one LDS base (m0) and differ in the instruction's immediate
+// offset, which the hardware adds to the global AND the LDS address.  Only the
+// copy's last chunk can be partial, and only it is lane-masked.
+constexpr int kChunkBytes = kWave * 16;
+template <int K>  // K chunks from one base: immediates 0, 1 KiB, ..
+__device__ __forceinline__ void lds_dma_group(const float4* gp, float4* lp) {
+    __builtin_amdgcn_global_load_lds((gbl_void_t*)gp, (lds_void_t*)lp, 16, 0, 0);
+    if (K > 1) __builtin_amdgcn_global_load_lds((gbl_void_t*)gp, (lds_void_t*)lp, 16, kChunkBytes, 0);
+    if (K > 2) __builtin_amdgcn_global_load_lds((gbl_void_t*)gp, (lds_void_t*)lp, 16, 2 * kChunkBytes, 0);
+    if (K > 3) __builtin_amdgcn_global_load_lds((gbl_void_t*)gp, (lds_void_t*)lp, 16, 3 * kChunkBytes, 0);
+}
+// full chunks [a, b) of the copy, no wrap (gl: the lane's float4 of chunk 0)
+__device__ __forceinline__ void lds_dma_segment(const float4* gl, float4* lds, int a, int b) {
+    const float4* gp = gl + a * kWave;
+    float4* lp = lds + a * kWave;
+    int n = b - a;
+    for (; n >= 4; n -= 4, gp += 4 * kWave, lp += 4 * kWave) lds_dma_group<4>(gp, lp);
+    if (n & 2) {
+        lds_dma_group<2>(gp, lp);
+        gp += 2 * kWave;
+        lp += 2 * kWave;
+    }
+    if (n & 1) lds_dma_group<1>(gp, lp);
+}
 __device__ __forceinline__ void lds_dma_copy(const float* __restrict__ g, float4* lds, int n4,
                                              int nw = kQueryThreads / kWave) {
     // nw: waves per block (a compile-time default: reading blockDim costs a
@@ -387,13 +416,20 @@ __device__ __forceinline__ void lds_dma_copy(const float* __restrict__ g, float4
     const int lane = threadIdx.x & (kWave - 1);
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
     const int nchunk = (n4 + kWave - 1) / kWave;
-    for (int c0 = wave; c0 < nchunk; c0 += nw) {
-        const int c = (c0 + (int)blockIdx.x) % nchunk;
-        const int i = c * kWave + lane;
-        if (i < n4 && CBN_OK_OR(i >= 0, 0))
-            __builtin_amdgcn_global_load_lds((gbl_void_t*)(g + (size_t)i * 4), (lds_void_t*)(lds + c * kWave), 16,
-                                             0, 0);
-    }
+    const int run = (nchunk + nw - 1) / nw;  // chunks per wave
+    const int r0 = wave * run;               // this wave's run, before the rotation
+    const int len = nchunk - r0 < run ? nchunk - r0 : run;
+    if (len <= 0 || !CBN_OK_OR(n4 > 0 && wave < nw, 0)) return;  // (fewer chunks than waves)
+    int start = r0 + (int)(blockIdx.x % (unsigned)nchunk);
+    if (start >= nchunk) start -= nchunk;
+    const int over = start + len - nchunk;  // > 0: the run wraps, chunks [0, over) come last
+    const int tail = n4 & (kWave - 1);      // float4 in the copy's last chunk when it is partial
+    const float4* gl = reinterpret_cast<const float4*>(g) + lane;
+    // the run reaches the last chunk and that chunk is partial: it is issued masked
+    const bool masked = over >= 0 && tail != 0;
+    lds_dma_segment(gl, lds, start, (over >= 0 ? nchunk : start + len) - (masked ? 1 : 0));
+    if (masked && lane < tail) lds_dma_group<1>(gl + (nchunk - 1) * kWave, lds + (nchunk - 1) * kWave);
+    if (over > 0) lds_dma_segment(gl, lds, 0, over);
 }
 
 // ---------------------------------------------------------------- fit ------
@@ -1844,9 +1880,9 @@ k_query_slots(int nf, int ns, const float* __restrict__ gimage, int qslot_off, c
 // queries) belongs to wave u % 16, whose factor is wave-uniform, so its column
 // pointer and record come in on the scalar path, its loads are coalesced
 // 256-B requests, and the domain index + table offset is computed right
-// there; the offsets go to LDS ([query][slot], int2-readable).  The evidence
-// loads are issued BEFORE the image's LDS-DMA, so both latencies overlap, and
-// ONE block barrier covers both.
+// there; the offsets go to LDS ([query][slot], int2-readable).  Every wave
+// issues its share of the image's LDS-DMA first, then its evidence loads, so
+// both latencies overlap, and ONE block barrier covers both.
 //
 // Products (conflict-free, no selects): a factor f's rows live in bank half
 // f & 1 (the paired layout).  The four queries of a ds_read_b128 lane group
@@ -1862,12 +1898,12 @@ k_query_slots(int nf, int ns, const float* __restrict__ gimage, int qslot_off, c
 constexpr int kSR = 256;  // queries per block round
 constexpr int kSQ = 128;  // queries per staging unit (two per lane)
 constexpr int kSU = 4;    // staging units per wave per round (nf <= 32 -> nf * 2 / 16 <= 4)
-#ifndef CBN_DMA_WAVES
-#define CBN_DMA_WAVES 4  // A/B on the headline (tools/ab_libs.sh): 1: 15.7, 2: 11.4, 3: 10.35, 4: 10.1, 8: 10.5-11.3, 12: 12.1 us; not split: 10.3 us
-#endif
-constexpr int kDmaW = CBN_DMA_WAVES;                 // round 0: waves issuing the image's LDS-DMA
-constexpr int kEvW = kQueryThreads / kWave - kDmaW;  // round 0: waves staging the evidence
-constexpr int kSUp = (64 + kEvW - 1) / kEvW;         // round 0: units per evidence wave
+// Round 0 with the straight-line fill (lds_dma_copy), A/B on the headline, us
+// per step | per back-to-back launch, medians of three alternating runs: the
+// fill split off into 1 / 2 / 4 dedicated DMA waves 9.66 | 9.49, 9.71 | 9.57,
+// 9.38 | 9.25; not split (kept: all 16 waves issue 5 chunks each, then stage
+// with kSU units) 9.27 | 9.04; the parent (4 DMA waves, modulo-loop fill) 9.45 |
+// 9.27.  MEASUREMENTS.md, "The image fill as straight-line DMA".
 
 // A raw launch of the pipelined sharded stepper also finishes an EARLIER step:
 // it divides that step's unnormalised rows (n4 float4, this block's slice of
@@ -1920,11 +1956,10 @@ k_query_staged(const float* __restrict__ gimage, int image_floats, int rec_off, 
     // (argument block) are wave-uniform scalar loads, all issued before the
     // first is used.  Tags: kTagNone (no observed parent: a dummy column, row
     // 0), kTagMore (further parents, rare: loaded in stage_store).
-    // Unit k of a wave = u = gw + k * GW (gw: the wave's index in a group of
-    // GW waves that stages a round; KSU * GW >= 64 >= nunits).  Round 0 is
-    // staged by the kEvW evidence waves alone (KSU = kSUp) while the other
-    // waves issue the image's LDS-DMA; later rounds by all 16 waves (kSU).
-    float x[kSUp][2] = {};
+    // Unit k of a wave = u = gw + k * GW (gw: the wave's index in the group of
+    // GW waves that stages a round; KSU * GW >= 64 >= nunits): all 16 waves,
+    // kSU units each.
+    float x[kSU][2] = {};
     auto stage_load = [&](long long qr, auto ksu, int gw, int GW) {
         constexpr int KSU = decltype(ksu)::value;
         // (unconditional: u / 2 < 32 stays inside the table whatever nf is, so
@@ -2016,6 +2051,21 @@ k_query_staged(const float* __restrict__ gimage, int image_floats, int rec_off, 
         }
     };
 
+    // Round 0: every wave issues its share of the image's LDS-DMA at once (the
+    // address is a preloaded argument; 5 chunks per wave on the headline), then
+    // its evidence loads (their column pointers are kernel arguments beyond the
+    // preloaded ones: a memory round trip, during which the fill is already in
+    // flight).  A wave's vector-memory counter drains in issue order, but the
+    // L2-served fill lands before the evidence does, so staging does not wait
+    // for it.  The padding slots are written behind both, not in front of the fill.
+    long long qr = q0;
+#ifndef CBN_ABL_NODMA
+    lds_dma_copy(gimage, smem4, image_floats / 4);  // tables + zero/ones rows + domains + records
+#endif
+#ifndef CBN_ABL_NOSTAGE
+    if (qr < q1) stage_load(qr, std::integral_constant<int, kSU>{}, wid, kQueryThreads / kWave);
+#endif
+    CBN_STAMP(1);
     // padding slots (constant for the launch, both buffers): slot 0 of a lagged
     // query and every slot past its last factor point at the ones row of the
     // slot's bank half (slot j of a query with lag d holds factor j - d)
@@ -2030,30 +2080,8 @@ k_query_staged(const float* __restrict__ gimage, int image_floats, int rec_off, 
             }
         }
     }
-    // evidence loads first, then the image's LDS-DMA: both latencies overlap
-    // (a wave's vector-memory counter drains in issue order, so loads issued
-    // after the DMA could not be consumed before it lands)
-    // Round 0, warp-specialised: waves [0, kDmaW) issue the image's LDS-DMA at
-    // once (its address is a preloaded argument), waves [kDmaW, 16) load and
-    // stage the evidence (their column pointers are kernel arguments beyond the
-    // preloaded ones: a memory round trip before the first load can issue).
-    // Each wave's vector-memory counter then holds only its own kind of load,
-    // so staging never waits for the DMA and the DMA never waits for the
-    // argument fetch.
-    long long qr = q0;
-    const bool dma_wave = wid < kDmaW;  // wave-uniform
-    if (!dma_wave) {
-#ifndef CBN_ABL_NOSTAGE
-        if (qr < q1) stage_load(qr, std::integral_constant<int, kSUp>{}, wid - kDmaW, kEvW);
-#endif
-    } else {
-#ifndef CBN_ABL_NODMA
-        lds_dma_copy(gimage, smem4, image_floats / 4, kDmaW);  // tables + zero/ones rows + domains + records
-#endif
-    }
-    CBN_STAMP(1);
-    if (!dma_wave && qr < q1)  // (CBN_ABL_NOSTAGE: x uninitialised, offsets still in range)
-        stage_store(qr, 0, std::integral_constant<int, kSUp>{}, wid - kDmaW, kEvW);
+    if (qr < q1)  // (CBN_ABL_NOSTAGE: x uninitialised, offsets still in range)
+        stage_store(qr, 0, std::integral_constant<int, kSU>{}, wid, kQueryThreads / kWave);
     CBN_STAMP(2);
     __syncthreads();  // image landed (vmcnt(0) of the DMA) + round 0 offsets
     CBN_STAMP(3);

@@ -38,8 +38,16 @@ for i in range(40):
 torch.cuda.synchronize()
 nat.check(lib.cbn_debug_set_stamp_buffer(ctypes.c_void_p(buf.data_ptr())), "stamps")
 buf.zero_()
-bn.infer(target, evs[3], N_max=NM)
+# BACKLOG=K: the stamps of the LAST of K launches enqueued behind a spin kernel
+# that holds the stream until the host is done (the queue stays full, as in
+# bench.py's backlogged_launch_us), instead of one launch after an idle GPU
+K = int(os.environ.get("BACKLOG", "1"))
+if K > 1:
+    torch.cuda._sleep(int(os.environ.get("BACKLOG_SPIN", 40_000_000)))
+for i in range(K):
+    bn.infer(target, evs[(3 + i) % 8], N_max=NM)
 torch.cuda.synchronize()
+print("launches enqueued:", K, "(stamps of the last one)" if K > 1 else "(after an idle GPU)")
 st = buf.view(-1, S).cpu().numpy()
 st = st[st[:, 0] > 0]
 print("waves stamped:", len(st), "fused" if bn.engine.fused else "two-pass (write pass stamps)")
@@ -74,8 +82,10 @@ late = np.argsort(e)[-8:]
 print("latest-entering blocks:", late.tolist(), (e[late] - t0).tolist())
 grp = np.array([e[b::8].min() - t0 for b in range(8)])
 print("first block entry per b % 8 group:", grp.tolist())
-# prologue by wave role (staged kernel: waves 0..3 issue the image DMA, 4..15 stage the evidence)
-for name, ws in (("DMA waves 0-3", slice(0, 4)), ("evidence waves 4-15", slice(4, 16))):
+# prologue by wave (staged kernel: every wave issues its share of the image DMA and stages evidence;
+# waves 0..3 also write the padding slots between stamps 1 and 2).  Before the straight-line fill,
+# waves 0..3 only issued the DMA and waves 4..15 only staged.
+for name, ws in (("waves 0-3", slice(0, 4)), ("waves 4-15", slice(4, 16))):
     sub = full[:nb, ws, :].reshape(-1, S)
     parts = []
     for k in (1, 2, 3):
