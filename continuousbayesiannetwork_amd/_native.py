@@ -170,6 +170,13 @@ _SIGNATURES = {
     "cbn_plan_argmax_scratch": (ctypes.c_int64, [ctypes.c_void_p, ctypes.c_int64]),
     "cbn_row_argmax": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p,
                                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "cbn_plan_run_moments": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int32,
+                                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p]),
+    "cbn_plan_moments_scratch": (ctypes.c_int64, [ctypes.c_void_p, ctypes.c_int64]),
+    "cbn_row_moments": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p,
+                                       ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                       ctypes.c_void_p]),
     "cbn_plan_create_param": (ctypes.c_int, [ctypes.POINTER(ParamFactor), ctypes.c_int32, ctypes.c_int32,
                                              ctypes.POINTER(ctypes.c_void_p)]),
     "cbn_param_eval": (ctypes.c_int, [ctypes.POINTER(ParamModel), ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32,
@@ -193,6 +200,7 @@ CBN_PLAN_FUSED, CBN_PLAN_PARAMETRIC, CBN_PLAN_VPL2, CBN_PLAN_DIRECT = 16, 32, 64
 CBN_PLAN_COLS = 256
 CBN_PLAN_SLOTS = 512
 CBN_PLAN_ARGMAX = 1024
+CBN_PLAN_MOMENTS = 2048
 CBN_E_ARG = -1
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

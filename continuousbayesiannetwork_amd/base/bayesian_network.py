@@ -201,3 +201,45 @@ class BayesianNetwork:
         if not out:
             return np.zeros((0,))
         return torch.cat(out).cpu().numpy().astype(np.float64)
+
+    def posterior(self, target_node: str, evidence: Dict[str, torch.Tensor] = None, N_max: int = 16):
+        """The target's marginal per evidence row as a distribution over its
+        sample points: ``infer``'s unnormalised rows, each divided by its OWN
+        sum instead of the batch maximum, so every row sums to 1 and does not
+        depend on the other queries of the call (``InferenceEngine.posterior``).
+        A row without support (off-domain evidence) is NaN.
+
+        :param evidence: {node: tensor [n_queries, 1]}, as ``infer``
+        :return: (pdf [n_queries, N_max], target domain [n_queries or 1, N_max]): ``infer``'s shapes
+        """
+        pdf, _, _, _, domain = self.engine.posterior_domain(target_node, evidence, N_max)
+        return pdf, domain
+
+    def expect(self, target_node: str, evidence: Dict[str, torch.Tensor] = None, N_max: int = 16,
+               moments: bool = False):
+        """The posterior mean of the target per evidence row -- the regression
+        estimate over the target's sample points, where ``predict`` gives the
+        most probable one -- in one launch that stores no [n_queries, N_max]
+        pdf (``InferenceEngine.posterior``).
+
+        :param evidence: {node: tensor [n_queries, 1]}, as ``infer``
+        :param moments: also return the posterior variance and each row's
+            unnormalised mass (0 for a row without support, whose mean and
+            variance are NaN)
+        :return: mean [n_queries], or (mean, var, mass)
+        """
+        _, mass, mean, var = self.engine.posterior(target_node, evidence, N_max, rows=False)
+        return (mean, var, mass) if moments else mean
+
+    def expect_df(self, data: pd.DataFrame, target_feature: str, batch_size: int = 128, N_max: int = 16) -> np.ndarray:
+        """``predict_df``'s interface and return type on ``expect``: the
+        posterior mean of the target per row."""
+        feats = [f for f in data.columns if f != target_feature]
+        values = {f: torch.tensor(data[f].values).unsqueeze(-1).to(device=self.device, dtype=torch.float32)
+                  for f in feats}
+        out = []
+        for n in range(0, len(data), batch_size):  # (the last batch may be short)
+            out.append(self.expect(target_feature, {f: values[f][n:n + batch_size] for f in feats}, N_max=N_max))
+        if not out:
+            return np.zeros((0,))
+        return torch.cat(out).cpu().numpy().astype(np.float64)

@@ -273,6 +273,104 @@ __device__ __forceinline__ void argmax_store(const float (&acc)[4 * NB], const i
     }
 }
 
+// ---- moments epilogue (kModeMoments launches, k_row_moments) ---------------
+// Where a posterior's per-query outputs go.  With raw[q, :] the unnormalised
+// product row and s_j = tv[j] the target's sample points:
+//   mass[q] = sum_j raw[q, j]                              (required)
+//   mean[q] = (sum_j raw[q, j] s_j) / mass[q]              (skipped when tv or mean is null)
+//   var[q]  = (sum_j raw[q, j] (s_j - mean[q])^2) / mass[q] (skipped when tv or var is null)
+// all accumulated in fp32, the variance in the centred two-pass form.  The
+// normalised row raw[q, :] / mass[q] goes to the launch's `out` when that is
+// not null.  A row of mass 0 follows IEEE: 0 / 0 = NaN in the row, mean and var.
+struct MomentsOut {
+    const float* tv;
+    float* mass;
+    float* mean;
+    float* var;
+};
+
+// The query kernels' last argument: the outputs of the one mode that has some
+// beyond `out` and the max words (the member the launch's MODE reads).
+union ModeOut {
+    ArgmaxOut am;
+    MomentsOut mo;
+};
+
+template <int CTRL>
+__device__ __forceinline__ float dpp_f32(float v) {
+    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, false));
+}
+
+// Sum over one query's L lanes (the segments of seg_max_key: L consecutive
+// lanes of one wave, 64 a multiple of L), in EVERY lane of the query: a
+// butterfly, whose two partners of a step add the same two values (fp addition
+// commutes), so all L lanes end with the same bits and the total depends on
+// nothing but the L values and their positions in the query.  L = 2 and 4:
+// quad_perm DPP steps; else an xor-shuffle ladder.  Valid for any
+// 1 <= L <= 64; every lane of the wave must be active.
+__device__ __forceinline__ float seg_sum(float v, int L) {
+    if (L == 1) return v;
+    if (L == 2) return v + dpp_f32<0xB1>(v);  // quad_perm [1, 0, 3, 2]
+    if (L == 4) {
+        v = v + dpp_f32<0xB1>(v);
+        return v + dpp_f32<0x4E>(v);  // quad_perm [2, 3, 0, 1]
+    }
+    for (int o = 1; o < L; o <<= 1) v = v + __shfl_xor(v, o, kWave);
+    return v;
+}
+
+// The moments launch's epilogue: acc[4 v + i] is the product of column
+// colv[v] + i of query q (argmax_store's layout).  A lane sums each 4-column
+// block in ascending column order and then adds the (at most two) block sums:
+// the paired layouts swap colv[0] and colv[1] with the query slot's parity, and
+// a + b == b + a, so a row's bits do not depend on its slot.  Every lane of
+// the query gets the totals (seg_sum) and divides its own columns: 16-B stores
+// at the raw mode's columns when `out` is not null (wave-uniform).  Called by
+// every lane of the wave; `valid`: the lane holds a query of the batch, `ok`:
+// and may store its columns.
+template <int NB>
+__device__ __forceinline__ void moments_store(const float (&acc)[4 * NB], const int (&colv)[NB], int l, int L, bool valid,
+                                              bool ok, long long q, int N, float* __restrict__ out,
+                                              const MomentsOut& mo) {
+    static_assert(NB <= 2, "more than two blocks: the order of the block sums would depend on colv");
+    auto lane_sum = [&](auto term) {
+        float t = 0.f;
+#pragma unroll
+        for (int v = 0; v < NB; ++v) {
+            const float b = ((term(v, 0) + term(v, 1)) + term(v, 2)) + term(v, 3);
+            t = v == 0 ? b : t + b;
+        }
+        return seg_sum(t, L);
+    };
+    const float mass = lane_sum([&](int v, int i) { return acc[4 * v + i]; });
+    float mean = 0.f, var = 0.f;
+    if (mo.tv && (mo.mean || mo.var)) {  // kernel-uniform
+        float s[4 * NB];  // the sample points of this lane's columns
+#pragma unroll
+        for (int v = 0; v < NB; ++v)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) s[4 * v + i] = mo.tv[colv[v] + i];
+        mean = lane_sum([&](int v, int i) { return acc[4 * v + i] * s[4 * v + i]; }) / mass;
+        if (mo.var)
+            var = lane_sum([&](int v, int i) {
+                      const float d = s[4 * v + i] - mean;
+                      return acc[4 * v + i] * (d * d);
+                  }) / mass;
+    }
+    if (out && ok) {
+        float* o = out + q * N;
+#pragma unroll
+        for (int v = 0; v < NB; ++v)
+            *reinterpret_cast<float4*>(o + colv[v]) = make_float4(acc[4 * v] / mass, acc[4 * v + 1] / mass,
+                                                                  acc[4 * v + 2] / mass, acc[4 * v + 3] / mass);
+    }
+    if (valid && l == 0) {
+        mo.mass[q] = mass;
+        if (mo.tv && mo.mean) mo.mean[q] = mean;
+        if (mo.tv && mo.var) mo.var[q] = var;
+    }
+}
+
 // Diagnostic build only (-DCBN_STAMPS): per-wave s_memtime stamps of the query
 // kernels' phases into a debug buffer (never read by the kernels themselves).
 #ifdef CBN_STAMPS
@@ -790,7 +888,10 @@ constexpr int kLoc = 8;
 // products in the same order, no grid barrier -- but instead of the row it
 // stores each query's (index, value, row_max) (argmax_store) and publishes no
 // max words: a prediction needs neither the batch max nor the division.
-constexpr int kModeMax = 0, kModeWrite = 1, kModeFused = 2, kModeRaw = 3, kModeArgmax = 4;
+// MODE 5 (moments): launched like the raw mode too; each query's row is reduced
+// to (mass, mean, var) and, when `out` is given, stored divided by its OWN sum
+// (moments_store).  Rows are independent of each other: no max words either.
+constexpr int kModeMax = 0, kModeWrite = 1, kModeFused = 2, kModeRaw = 3, kModeArgmax = 4, kModeMoments = 5;
 constexpr unsigned kSpinLimit = 1u << 22;  // bounded barrier spin (~0.3 s): never hang
 
 // Fused grid barrier on the global max, called by ONE wave per block (all
@@ -874,6 +975,7 @@ __device__ __forceinline__ unsigned slot_barrier_max(unsigned* __restrict__ sync
 //   kModeFused   both in one launch: the products wait in registers for the grid barrier
 //   kModeRaw     the unnormalised rows and the per-block maxima (a scale pass divides)
 //   kModeArgmax  per query the first column of the row maximum (ArgmaxOut), no rows
+//   kModeMoments per query mass / mean / var (MomentsOut) and, with `out`, the row / its own sum
 // What a mode does with a lane's products is the same in every kernel and lives
 // here.  lane / wid / tid / nthr are the caller's own values (k_query_fast
 // reads blockDim, the others know it at compile time).
@@ -916,8 +1018,9 @@ __device__ __forceinline__ void store_row_div(float* o, const int (&col)[VPL], c
 template <int VPL, int MODE>
 __device__ __forceinline__ void round_epilogue(const float (&acc)[4 * VPL], const int (&col)[VPL], int l, int L, bool valid,
                                                bool ok, long long q, int N, float* out, float maxv, float& lmax,
-                                               bool hold, long long& fq, const ArgmaxOut& am) {
-    if (MODE == kModeArgmax) argmax_store<VPL>(acc, col, l, L, valid, q, am);
+                                               bool hold, long long& fq, const ModeOut& mx) {
+    if (MODE == kModeArgmax) argmax_store<VPL>(acc, col, l, L, valid, q, mx.am);
+    if (MODE == kModeMoments) moments_store<VPL>(acc, col, l, L, valid, ok, q, N, out, mx.mo);
     if (ok) {
         if (MODE == kModeFused && hold) fq = q;
         if (MODE == kModeWrite) {
@@ -926,7 +1029,7 @@ __device__ __forceinline__ void round_epilogue(const float (&acc)[4 * VPL], cons
             store_row<VPL>(out + q * N, col, acc);
 #pragma unroll
             for (int i = 0; i < 4 * VPL; ++i) lmax = fmaxf(lmax, acc[i]);
-        } else if (MODE != kModeArgmax) {
+        } else if (MODE != kModeArgmax && MODE != kModeMoments) {
 #pragma unroll
             for (int i = 0; i < 4 * VPL; ++i) lmax = fmaxf(lmax, acc[i]);
         }
@@ -979,7 +1082,7 @@ __global__ void __launch_bounds__(kQueryThreads)
 k_query_fast(int rec_off, int nf, int ns, const float* __restrict__ gimage, int image_floats, FPtrsT<NP> fp,
              long long Q, long long per, int N, int RS, int L, int paired, unsigned* __restrict__ sync,
              unsigned epoch, const unsigned* __restrict__ max_in, int n_max, unsigned* __restrict__ max_out,
-             float* __restrict__ out, int lds_tab, unsigned long long lmask0, unsigned long long lmask1, ArgmaxOut am) {
+             float* __restrict__ out, int lds_tab, unsigned long long lmask0, unsigned long long lmask1, ModeOut mx) {
     CBN_STAMP_INIT;
     extern __shared__ __attribute__((aligned(16))) float4 smem4[];
     float* simg = reinterpret_cast<float*>(smem4);
@@ -1241,7 +1344,7 @@ k_query_fast(int rec_off, int nf, int ns, const float* __restrict__ gimage, int 
         }
         if (first) CBN_STAMP(5);
         const bool ok = valid && CBN_OK_OR(q < Q && (long long)(l + 1) * VPL * 4 <= N, 3);
-        round_epilogue<VPL, MODE>(acc, col, l, L, valid, ok, q, N, out, maxv, lmax, true, fq, am);  // (wave-uniform call site)
+        round_epilogue<VPL, MODE>(acc, col, l, L, valid, ok, q, N, out, maxv, lmax, true, fq, mx);  // (wave-uniform call site)
         __builtin_amdgcn_wave_barrier();  // next round rewrites this wave's offsets
         if (first) CBN_STAMP(6);
         first = false;
@@ -1310,7 +1413,7 @@ k_query_cols(int rec_off, int nf, int ns, const float* __restrict__ gimage, int 
              FPtrsT<kFastPtrsSmall> sp, long long Q, long long per, int N, int RS, int L,
              unsigned* __restrict__ sync, unsigned epoch, const unsigned* __restrict__ max_in, int n_max,
              unsigned* __restrict__ max_out, float* __restrict__ out, int lds_tab, const int* __restrict__ crec,
-             ArgmaxOut am) {
+             ModeOut mx) {
     CBN_STAMP_INIT;
     extern __shared__ __attribute__((aligned(16))) float4 smem4[];
     float* simg = reinterpret_cast<float*>(smem4);
@@ -1482,7 +1585,7 @@ k_query_cols(int rec_off, int nf, int ns, const float* __restrict__ gimage, int 
 #pragma unroll
             for (int i = 0; i < NV; ++i) acc0[i] = acc[i];
         }
-        round_epilogue<VPL, MODE>(acc, col, l, L, valid, valid, q, N, out, maxv, lmax, !first, fq, am);  // (wave-uniform call site)
+        round_epilogue<VPL, MODE>(acc, col, l, L, valid, valid, q, N, out, maxv, lmax, !first, fq, mx);  // (wave-uniform call site)
         // the next round rewrites this query slot's indices (lanes of one wave)
         __builtin_amdgcn_s_waitcnt(0xC07F);
         __builtin_amdgcn_wave_barrier();
@@ -1544,7 +1647,7 @@ k_query_slots(int nf, int ns, const float* __restrict__ gimage, int qslot_off, c
               FPtrsT<kFastPtrsSmall> sp, long long Q, long long per, int N, int L, unsigned* __restrict__ sync,
               unsigned epoch, const unsigned* __restrict__ max_in, int n_max, unsigned* __restrict__ max_out,
               float* __restrict__ out, int lds_tab, unsigned long long lmask0, unsigned long long lmask1, int coal,
-              ArgmaxOut am) {
+              ModeOut mx) {
     CBN_STAMP_INIT;
     extern __shared__ __attribute__((aligned(16))) float4 smem4[];
     float* simg = reinterpret_cast<float*>(smem4);
@@ -1850,7 +1953,7 @@ k_query_slots(int nf, int ns, const float* __restrict__ gimage, int qslot_off, c
 #pragma unroll
             for (int i = 0; i < NV; ++i) acc0[i] = acc[i];
         }
-        round_epilogue<VPL, MODE>(acc, col, l, L, valid, valid, q, N, out, maxv, lmax, !first, fq, am);  // (wave-uniform call site)
+        round_epilogue<VPL, MODE>(acc, col, l, L, valid, valid, q, N, out, maxv, lmax, !first, fq, mx);  // (wave-uniform call site)
         // the next round rewrites this query slot's indices and offsets (lanes of one wave)
         __builtin_amdgcn_s_waitcnt(0xC07F);
         __builtin_amdgcn_wave_barrier();
@@ -1928,7 +2031,7 @@ __global__ void __launch_bounds__(kQueryThreads)
 k_query_staged(const float* __restrict__ gimage, int image_floats, int rec_off, int nf, int zero_off, long long Q,
                long long per, unsigned* __restrict__ sync, unsigned epoch, const unsigned* __restrict__ max_in,
                int n_max, unsigned* __restrict__ max_out, float* __restrict__ out, FoldJob fold,
-               FPtrsT<kFastPtrsSmall> fp, ArgmaxOut am) {
+               FPtrsT<kFastPtrsSmall> fp, ModeOut mx) {
     CBN_STAMP_INIT;
     constexpr int N = 32;
     extern __shared__ __attribute__((aligned(16))) float4 smem4[];
@@ -2196,7 +2299,11 @@ k_query_staged(const float* __restrict__ gimage, int image_floats, int rec_off, 
             // an aligned quad holds the row; for odd query slots clo > chi, so the
             // keys carry the column numbers, not the register positions
             const int colv[2] = {clo, chi};
-            argmax_store<2>(acc, colv, l, 4, q < q1, q, am);
+            argmax_store<2>(acc, colv, l, 4, q < q1, q, mx.am);
+        }
+        if (MODE == kModeMoments) {  // (the sums are by block, so the clo / chi order does not show)
+            const int colv[2] = {clo, chi};
+            moments_store<2>(acc, colv, l, 4, q < q1, q < q1, q, N, out, mx.mo);
         }
         if (q < q1) {
             if (MODE == kModeFused) fq = q;
@@ -2215,7 +2322,7 @@ k_query_staged(const float* __restrict__ gimage, int image_floats, int rec_off, 
                     ? make_float4(acc[4] / dv, acc[5] / dv, acc[6] / dv, acc[7] / dv)
                     : make_float4(acc[4], acc[5], acc[6], acc[7]);
             }
-            if (MODE != kModeWrite && MODE != kModeArgmax)
+            if (MODE != kModeWrite && MODE != kModeArgmax && MODE != kModeMoments)
 #pragma unroll
                 for (int i = 0; i < 8; ++i) lmax = fmaxf(lmax, acc[i]);
         }
@@ -2447,6 +2554,70 @@ k_row_argmax(const float* __restrict__ rows, long long n_rows, int n_cols, int L
     }
 }
 
+// (mass, mean, var) of stored raw rows [n_rows, n_cols] (MomentsOut), and with
+// `normalize` each row divided IN PLACE by its mass: the posterior of every
+// plan without a moments epilogue in its query kernel (generic, direct,
+// wide-column and parametric plans).  Plain float arithmetic, so a NaN or inf
+// of a parametric row propagates through that row's outputs and no further.
+// The split of a row over lanes is k_row_argmax's (VEC: lane l of LR takes the
+// 16-B pieces l, l + LR, ...; else one lane walks the row), a function of
+// n_cols alone, and seg_sum gives every lane the totals: a row's outputs do
+// not depend on where it sits in the batch.  The row is read once per sum
+// (mass, then the mean's, then the centred variance's) and once more to divide.
+template <bool VEC>
+__global__ void __launch_bounds__(kRowThreads)
+k_row_moments(float* rows, long long n_rows, int n_cols, int LR, int normalize, MomentsOut mo) {
+    const int l = VEC ? (int)(threadIdx.x & (unsigned)(LR - 1)) : 0;
+    const long long rpb = kRowThreads / LR;
+    const bool centred = mo.tv && (mo.mean || mo.var);  // kernel-uniform
+    // (block-uniform trip count: every lane stays active for the DPP steps)
+    for (long long r0 = (long long)blockIdx.x * rpb; r0 < n_rows; r0 += (long long)gridDim.x * rpb) {
+        const long long rr = r0 + threadIdx.x / LR;
+        const bool valid = rr < n_rows;
+        const long long r = valid ? rr : n_rows - 1;
+        float* row = rows + r * n_cols;
+        float4* row4 = reinterpret_cast<float4*>(row);
+        // sum over the lane's columns of term(raw, column), then over the row's lanes
+        auto row_sum = [&](auto term) {
+            float t = 0.f;
+            if (VEC) {
+                for (int c4 = l; c4 < n_cols / 4; c4 += LR) {
+                    const float4 a = row4[c4];
+                    t += ((term(a.x, 4 * c4) + term(a.y, 4 * c4 + 1)) + term(a.z, 4 * c4 + 2)) + term(a.w, 4 * c4 + 3);
+                }
+                return seg_sum(t, LR);
+            }
+            for (int c = 0; c < n_cols; ++c) t += term(row[c], c);
+            return t;
+        };
+        const float mass = row_sum([](float a, int) { return a; });
+        float mean = 0.f, var = 0.f;
+        if (centred) {
+            mean = row_sum([&](float a, int c) { return a * mo.tv[c]; }) / mass;
+            if (mo.var)
+                var = row_sum([&](float a, int c) {
+                          const float d = mo.tv[c] - mean;
+                          return a * (d * d);
+                      }) / mass;
+        }
+        if (normalize && valid) {
+            if (VEC) {
+                for (int c4 = l; c4 < n_cols / 4; c4 += LR) {
+                    const float4 a = row4[c4];
+                    row4[c4] = make_float4(a.x / mass, a.y / mass, a.z / mass, a.w / mass);
+                }
+            } else {
+                for (int c = 0; c < n_cols; ++c) row[c] = row[c] / mass;
+            }
+        }
+        if (valid && l == 0) {
+            mo.mass[r] = mass;
+            if (mo.tv && mo.mean) mo.mean[r] = mean;
+            if (mo.tv && mo.var) mo.var[r] = var;
+        }
+    }
+}
+
 int g_num_cu = 0;
 
 }  // namespace
@@ -2463,6 +2634,25 @@ static int launch_row_argmax(const float* rows, long long n_rows, int n_cols, co
         hipLaunchKernelGGL(k_row_argmax<true>, dim3((unsigned)blocks), dim3(kRowThreads), 0, s, rows, n_rows, n_cols, LR, am);
     else
         hipLaunchKernelGGL(k_row_argmax<false>, dim3((unsigned)blocks), dim3(kRowThreads), 0, s, rows, n_rows, n_cols, LR, am);
+    HIP_TRY(hipGetLastError());
+    return CBN_OK;
+}
+
+// mass / mean / var of rows [n_rows, n_cols] on `s`, the rows divided in place when `normalize` (k_row_moments)
+static int launch_row_moments(float* rows, long long n_rows, int n_cols, bool normalize, const MomentsOut& mo,
+                              hipStream_t s) {
+    const bool vec = n_cols % 4 == 0 && reinterpret_cast<uintptr_t>(rows) % 16 == 0;
+    int LR = 1;
+    if (vec)
+        while (LR < n_cols / 4 && LR < kWave) LR <<= 1;
+    const long long rpb = kRowThreads / LR;
+    const long long blocks = std::max(1LL, std::min((n_rows + rpb - 1) / rpb, (long long)num_cu() * 16));
+    if (vec)
+        hipLaunchKernelGGL(k_row_moments<true>, dim3((unsigned)blocks), dim3(kRowThreads), 0, s, rows, n_rows, n_cols, LR,
+                           normalize ? 1 : 0, mo);
+    else
+        hipLaunchKernelGGL(k_row_moments<false>, dim3((unsigned)blocks), dim3(kRowThreads), 0, s, rows, n_rows, n_cols, LR,
+                           normalize ? 1 : 0, mo);
     HIP_TRY(hipGetLastError());
     return CBN_OK;
 }
@@ -2537,18 +2727,20 @@ size_t slots_lds_bytes(long long lds_tab_floats, int ns, int nf, int QB) {
 template <int VPL, bool LDS, int MODE, int NP>
 void launch_fast_np(const cbn_plan* p, unsigned blocks, hipStream_t s, const EvPtrs& ev, long long Q, int L,
                     unsigned epoch, const unsigned* max_in, int n_max, unsigned* max_out, float* out,
-                    const ArgmaxOut& am) {
+                    const ModeOut& mx) {
     hipLaunchKernelGGL((k_query_fast<VPL, LDS, MODE, NP>), dim3(blocks), dim3(kQueryThreads), p->fast_lds_bytes, s,
                        p->rec_off, p->nf, p->ns, p->d_image, p->image_floats, fast_ptrs<NP>(p, ev), Q,
                        (Q + blocks - 1) / blocks, p->N, p->RS, L, p->paired ? 1 : 0, p->d_sync, epoch, max_in, n_max,
-                       max_out, out, p->lds_tab_floats, p->lds_tab_mask[0], p->lds_tab_mask[1], am);
+                       max_out, out, p->lds_tab_floats, p->lds_tab_mask[0], p->lds_tab_mask[1], mx);
 }
 
 template <int VPL, bool LDS, int MODE>
 void launch_fast_k(const cbn_plan* p, unsigned blocks, hipStream_t s, const EvPtrs& ev, long long Q, int L,
                    unsigned epoch, const unsigned* max_in, int n_max, unsigned* max_out, float* out,
-                   const FoldJob* fold = nullptr, const ArgmaxOut* amp = nullptr) {
-    const ArgmaxOut am = amp ? *amp : ArgmaxOut{nullptr, nullptr, nullptr, nullptr};  // (read by kModeArgmax only)
+                   const FoldJob* fold = nullptr, const ModeOut* mxp = nullptr) {
+    ModeOut mx;  // (read by kModeArgmax / kModeMoments only)
+    memset(&mx, 0, sizeof(mx));
+    if (mxp) mx = *mxp;
     if (p->staged) {  // paired N = 32 layout in LDS: the staged kernel (same grid, same words)
         FoldJob fj;
         memset(&fj, 0, sizeof(fj));
@@ -2560,7 +2752,7 @@ void launch_fast_k(const cbn_plan* p, unsigned blocks, hipStream_t s, const EvPt
         hipLaunchKernelGGL((k_query_staged<MODE>), dim3(blocks), dim3(kQueryThreads), p->staged_lds_bytes, s,
                            p->d_image, p->image_floats, p->rec_off + p->prefix * kRecFloats, p->nf - p->prefix,
                            p->zero_off, Q, (Q + blocks - 1) / blocks, p->d_sync, epoch, max_in, n_max, max_out, out,
-                           fj, fast_ptrs<kFastPtrsSmall>(p, ev, p->prefix), am);
+                           fj, fast_ptrs<kFastPtrsSmall>(p, ev, p->prefix), mx);
         return;
     }
     if (p->slots) {
@@ -2581,7 +2773,7 @@ void launch_fast_k(const cbn_plan* p, unsigned blocks, hipStream_t s, const EvPt
         hipLaunchKernelGGL((k_query_slots<VPL, MODE>), dim3(blocks), dim3(kQueryThreads), p->fast_lds_bytes, s, p->nf,
                            p->ns, p->d_image, p->rec_off + p->nf * kRecFloats, p->d_crec, slot_ptrs(p, ev), Q, per,
                            p->N, L, p->d_sync, epoch, max_in, n_max, max_out, out, p->lds_tab_floats,
-                           p->lds_tab_mask[0], p->lds_tab_mask[1], coal, am);
+                           p->lds_tab_mask[0], p->lds_tab_mask[1], coal, mx);
         return;
     }
     if (p->cols) {
@@ -2589,13 +2781,13 @@ void launch_fast_k(const cbn_plan* p, unsigned blocks, hipStream_t s, const EvPt
         hipLaunchKernelGGL(k, dim3(blocks), dim3(kQueryThreads), p->fast_lds_bytes, s,
                            p->rec_off, p->nf, p->ns, p->d_image, p->image_floats, slot_ptrs(p, ev), Q,
                            (Q + blocks - 1) / blocks, p->N, p->RS, L, p->d_sync, epoch, max_in, n_max, max_out, out,
-                           p->lds_tab_floats, p->d_crec, am);
+                           p->lds_tab_floats, p->d_crec, mx);
         return;
     }
     if (p->nf * kFastObs <= kFastPtrsSmall)
-        launch_fast_np<VPL, LDS, MODE, kFastPtrsSmall>(p, blocks, s, ev, Q, L, epoch, max_in, n_max, max_out, out, am);
+        launch_fast_np<VPL, LDS, MODE, kFastPtrsSmall>(p, blocks, s, ev, Q, L, epoch, max_in, n_max, max_out, out, mx);
     else
-        launch_fast_np<VPL, LDS, MODE, kFastPtrs>(p, blocks, s, ev, Q, L, epoch, max_in, n_max, max_out, out, am);
+        launch_fast_np<VPL, LDS, MODE, kFastPtrs>(p, blocks, s, ev, Q, L, epoch, max_in, n_max, max_out, out, mx);
 }
 
 template <int VPL, bool LDS, int MODE>
@@ -2656,15 +2848,16 @@ unsigned query_blocks(const cbn_plan* p, long long Q, int L, bool reserve) {
 //   kModeWrite   out = products / max(max_in[0, n_max)), the max published in *max_out when non-null
 //   kModeRaw     unnormalised rows -> out, per-block maxima -> max_out[0, max_slots);
 //                `fold`: an earlier step's rows to scale on the way (staged plans)
-//   kModeArgmax  `am` only: the raw launch's grid and rounds, no rows, no max words
+//   kModeArgmax  `mx->am` only: the raw launch's grid and rounds, no rows, no max words
+//   kModeMoments `mx->mo`, and out = products / the row's own sum when non-null: launched as kModeArgmax
 template <int MODE>
 int launch_mode(cbn_plan* p, long long Q, const EvPtrs& ev, const unsigned* max_in, int n_max, unsigned* max_out,
-                float* out, hipStream_t s, const FoldJob* fold = nullptr, const ArgmaxOut* am = nullptr) {
+                float* out, hipStream_t s, const FoldJob* fold = nullptr, const ModeOut* mx = nullptr) {
     if (MODE == kModeMax || MODE == kModeRaw) n_max = p->max_slots;
     with_variant(p, [&](auto vpl, auto lds) {
         const int L = p->N / (4 * vpl.value);
-        const unsigned blocks = query_blocks(p, Q, L, MODE == kModeRaw || MODE == kModeArgmax);
-        launch_fast_k<vpl.value, lds.value, MODE>(p, blocks, s, ev, Q, L, 0u, max_in, n_max, max_out, out, fold, am);
+        const unsigned blocks = query_blocks(p, Q, L, MODE == kModeRaw || MODE == kModeArgmax || MODE == kModeMoments);
+        launch_fast_k<vpl.value, lds.value, MODE>(p, blocks, s, ev, Q, L, 0u, max_in, n_max, max_out, out, fold, mx);
     });
     HIP_TRY(hipGetLastError());
     return CBN_OK;
@@ -2790,11 +2983,15 @@ void allow_lds(size_t bytes) {
         allow_fast_lds<2, LDS, kModeRaw>((int)bytes);
         allow_fast_lds<1, LDS, kModeArgmax>((int)bytes);
         allow_fast_lds<2, LDS, kModeArgmax>((int)bytes);
+        allow_fast_lds<1, LDS, kModeMoments>((int)bytes);
+        allow_fast_lds<2, LDS, kModeMoments>((int)bytes);
     }
 }
 
 // the plan's arg-max runs in its query kernel (kModeArgmax): every fast-path table plan
 bool argmax_native(const cbn_plan* p) { return p->fast && !p->param && !p->direct; }
+// ... and so do its moments (kModeMoments): the same plans
+bool moments_native(const cbn_plan* p) { return argmax_native(p); }
 
 // Rows of a factor's table: the product of its observed parents' cards
 // (clamped, so a sum over the factors cannot overflow).
@@ -3261,7 +3458,8 @@ int cbn_plan_create(const cbn_factor_desc* factors, int32_t n_factors, int32_t n
                                        reinterpret_cast<const void*>(&k_query_staged<kModeWrite>),
                                        reinterpret_cast<const void*>(&k_query_staged<kModeFused>),
                                        reinterpret_cast<const void*>(&k_query_staged<kModeRaw>),
-                                       reinterpret_cast<const void*>(&k_query_staged<kModeArgmax>)})
+                                       reinterpret_cast<const void*>(&k_query_staged<kModeArgmax>),
+                                       reinterpret_cast<const void*>(&k_query_staged<kModeMoments>)})
                     (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBudget);
             }
             P->fast_lds_bytes =
@@ -3587,7 +3785,69 @@ int cbn_plan_run_argmax(cbn_plan* plan, int64_t n_queries, const float* const* e
     }
     EvPtrs ev;
     CBN_TRY(pack_evidence(plan, evidence, n_evidence, n_queries, ev));
-    return launch_mode<kModeArgmax>(plan, n_queries, ev, nullptr, 0, nullptr, nullptr, s, nullptr, &am);
+    ModeOut mx;
+    mx.am = am;
+    return launch_mode<kModeArgmax>(plan, n_queries, ev, nullptr, 0, nullptr, nullptr, s, nullptr, &mx);
+}
+
+int cbn_row_moments(float* rows, int64_t n_rows, int32_t n_cols, const float* target_values, int32_t normalize,
+                    float* mass, float* mean, float* var, void* stream) {
+    if (n_rows < 0 || n_cols < 1 || (n_rows > 0 && (!rows || !mass)) || ((mean || var) && !target_values))
+        return set_err(CBN_E_ARG, "cbn_row_moments: bad arguments");
+    if (n_rows == 0) return CBN_OK;
+    const MomentsOut mo = {target_values, mass, mean, var};
+    return launch_row_moments(rows, (long long)n_rows, (int)n_cols, normalize != 0, mo,
+                              reinterpret_cast<hipStream_t>(stream));
+}
+
+int64_t cbn_plan_moments_scratch(const cbn_plan* plan, int64_t n_queries) {
+    if (!plan || n_queries < 0 || moments_native(plan)) return 0;
+    return n_queries * (int64_t)plan->N;
+}
+
+int cbn_plan_run_moments(cbn_plan* plan, int64_t n_queries, const float* const* evidence, int32_t n_evidence,
+                         const float* target_values, float* out, float* mass, float* mean, float* var, float* scratch,
+                         int32_t flags, void* stream) {
+    if (!plan) return set_err(CBN_E_ARG, "null plan");
+    if (!mass) return set_err(CBN_E_ARG, "cbn_plan_run_moments: null output");
+    if ((mean || var) && !target_values)
+        return set_err(CBN_E_ARG, "cbn_plan_run_moments: mean / var need the target's sample points");
+    if (n_queries <= 0) return set_err(CBN_E_ARG, "cbn_plan_run_moments: needs >= 1 query");
+    if (n_evidence < 0 || (n_evidence > 0 && !evidence)) return set_err(CBN_E_ARG, "cbn_plan_run_moments: null evidence");
+    for (int i = 0; i < n_evidence; ++i)
+        if (!evidence[i]) return set_err(CBN_E_ARG, "null evidence column %d", i);
+    const bool native = moments_native(plan);
+    float* rows = out ? out : scratch;  // fallback plans: where the raw rows go (divided in place when that is `out`)
+    if (!native && !rows)
+        return set_err(CBN_E_ARG, "cbn_plan_run_moments: this plan needs `out` or cbn_plan_moments_scratch floats of scratch");
+    if (native && reinterpret_cast<uintptr_t>(out) % 16)
+        return set_err(CBN_E_ARG, "cbn_plan_run_moments: out must be 16-B aligned");
+    const bool table = !plan->param && !plan->direct;
+    if (table) {
+        if (n_evidence != plan->ns) return set_err(CBN_E_ARG, "plan expects %d evidence columns, got %d", plan->ns, n_evidence);
+        if (!plan->d_fac || !plan->d_slots || !plan->d_image || !plan->d_sync)
+            return set_err(CBN_E_ARG, "plan has no device buffers");
+    }
+    CBN_TRY(take_pending_timeout(plan));
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const MomentsOut mo = {target_values, mass, mean, var};
+    if (!table) {
+        // direct / parametric plans: their raw launch (per-block maxima into the plan's own words, unused here)
+        CBN_TRY(cbn_plan_run(plan, n_queries, evidence, n_evidence, plan->d_sync + kMaxWordOff, rows,
+                             (flags & CBN_RUN_BUILD_TABLES) | CBN_RUN_RAW, stream));
+        return launch_row_moments(rows, (long long)n_queries, plan->N, out != nullptr, mo, s);
+    }
+    if (flags & CBN_RUN_BUILD_TABLES) CBN_TRY(cbn_plan_build_tables(plan, stream));
+    if (!native) {
+        // generic table plans: the write pass dividing by 1.0f stores the raw rows (IEEE x / 1 = x)
+        CBN_TRY(cbn_plan_query_write(plan, n_queries, evidence, n_evidence, plan->d_sync + kOneWordOff, rows, stream));
+        return launch_row_moments(rows, (long long)n_queries, plan->N, out != nullptr, mo, s);
+    }
+    EvPtrs ev;
+    CBN_TRY(pack_evidence(plan, evidence, n_evidence, n_queries, ev));
+    ModeOut mx;
+    mx.mo = mo;
+    return launch_mode<kModeMoments>(plan, n_queries, ev, nullptr, 0, nullptr, out, s, nullptr, &mx);
 }
 
 int cbn_plan_status(cbn_plan* plan, int32_t* status) {
@@ -3618,7 +3878,7 @@ int32_t cbn_plan_flags(const cbn_plan* plan) {
            (plan->fused_ok ? CBN_PLAN_FUSED : 0) | (plan->param ? CBN_PLAN_PARAMETRIC : 0) |
            (plan->vpl == 2 ? CBN_PLAN_VPL2 : 0) | (plan->direct ? CBN_PLAN_DIRECT : 0) |
            (plan->cols ? CBN_PLAN_COLS : 0) | (plan->slots ? CBN_PLAN_SLOTS : 0) |
-           (argmax_native(plan) ? CBN_PLAN_ARGMAX : 0);
+           (argmax_native(plan) ? CBN_PLAN_ARGMAX : 0) | (moments_native(plan) ? CBN_PLAN_MOMENTS : 0);
 }
 
 int32_t cbn_plan_max_words(const cbn_plan* plan) {

@@ -163,6 +163,36 @@ py::object run_argmax(uintptr_t fn, uintptr_t plan, py::dict evidence, py::tuple
     return py::make_tuple(index, value, row_max);
 }
 
+// InferenceEngine.posterior's hot path, run_argmax's sibling: run's evidence
+// checks, then mass, mean and var (float32 [Q]; tv_ptr: the target's float32
+// sample points on the device), the [Q, n_samples] pdf when `rows` -- else `scratch_per_query` floats of scratch per
+// query for plans without the moments epilogue (cbn_plan_moments_scratch) --
+// and ONE call of cbn_plan_run_moments (passed in as `fn`) on the current
+// stream.  Returns (pdf or None, mass, mean, var); None when a fast check
+// failed; an int = the C ABI's error code.
+using moments_fn = int (*)(void*, int64_t, const float* const*, int32_t, const float*, float*, float*, float*, float*,
+                           float*, int32_t, hipStream_t);
+
+py::object run_moments(uintptr_t fn, uintptr_t plan, py::dict evidence, py::tuple slots, py::object first,
+                       int64_t device_index, int64_t n_samples, bool target_observed, uintptr_t tv_ptr, bool rows,
+                       int64_t scratch_per_query, int32_t flags) {
+    Cols c;
+    if (!gather(evidence, slots, first, device_index, target_observed, c)) return py::none();
+    const auto fopt = at::TensorOptions().dtype(at::kFloat).device(at::Device(at::kCUDA, (c10::DeviceIndex)device_index));
+    at::Tensor mass = at::empty({c.n}, fopt), mean = at::empty({c.n}, fopt), var = at::empty({c.n}, fopt);
+    at::Tensor pdf, scratch;  // (scratch freed at return: stream-ordered behind the launches that use it)
+    if (rows) pdf = at::empty({c.n, n_samples}, fopt);
+    else if (scratch_per_query > 0) scratch = at::empty({c.n * scratch_per_query}, fopt);
+    auto p = [](const at::Tensor& t) { return t.defined() ? static_cast<float*>(t.data_ptr()) : nullptr; };
+    const hipStream_t s = c10::hip::getCurrentHIPStream(device_index).stream();
+    const int rc = reinterpret_cast<moments_fn>(fn)(reinterpret_cast<void*>(plan), c.n, c.p,
+                                                    (int32_t)PyTuple_GET_SIZE(slots.ptr()),
+                                                    reinterpret_cast<const float*>(tv_ptr), p(pdf), p(mass), p(mean),
+                                                    p(var), p(scratch), flags, s);
+    if (rc) return py::int_(rc);
+    return py::make_tuple(pdf.defined() ? py::cast(pdf) : py::object(py::none()), mass, mean, var);
+}
+
 using scale_fn = int (*)(float*, int64_t, const unsigned*, int32_t, hipStream_t);
 using scale_batch_fn = int (*)(float* const*, const int64_t*, int32_t, const unsigned*, int32_t, hipStream_t);
 
@@ -1224,6 +1254,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.doc() = "cbn MI355X host fast path (cached-plan infer)";
     m.def("run", &run);
     m.def("run_argmax", &run_argmax);
+    m.def("run_moments", &run_moments);
     m.def("scale", &scale);
     m.def("nccl_unique_id", &nccl_unique_id);
     m.def("nccl_comm_init", &nccl_comm_init);

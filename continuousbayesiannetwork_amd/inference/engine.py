@@ -215,7 +215,7 @@ class _FastPath:
     """Everything the hot path needs for one cached (target, evidence keys, N)."""
 
     __slots__ = ("plan", "device", "first", "ptrs", "max_ptr", "lib", "tdom", "host", "run_fn", "slot_keys",
-                 "scale_fn", "host_scale", "words", "redraw", "runner", "argmax")
+                 "scale_fn", "host_scale", "words", "redraw", "runner", "argmax", "moments")
 
     def __init__(self, plan: "Plan", device: torch.device, first_key):
         self.plan = plan
@@ -236,6 +236,7 @@ class _FastPath:
         self.words = torch.zeros(nw, dtype=torch.int32, device=device) if nw > 0 else None
         self.runner = None  # native Runner of this fast path (InferenceEngine._runner), built on first use
         self.argmax = None  # predict: (host_fast.run_argmax, cbn_plan_run_argmax, scratch floats per query)
+        self.moments = None  # posterior: (host_fast.run_moments, cbn_plan_run_moments, scratch floats per query)
 
 
 class InferenceEngine:
@@ -1040,11 +1041,11 @@ class InferenceEngine:
             value = plan.target_domain.to(fp.device)[index.long()]
         return index, value, row_max
 
-    def _predict(self, plan: Plan, evidence, n_queries: int, device):
-        """predict's general path, as ``_run``: [Q, N] columns on the wide
-        direct plan, conversions, the reference's shape errors -- all raised
-        before anything is launched."""
-        lib = _native.load()
+    def _general_call(self, plan: Plan, evidence, n_queries: int, device):
+        """What the general path of a per-query reduction (predict, posterior)
+        launches, as ``_run``: [Q, N] columns on the wide direct plan,
+        conversions, the reference's shape errors -- all raised before anything
+        is launched.  Returns (plan to run, device columns, flags)."""
         N = plan.n_samples
         wide = self._wide(plan, evidence)
         run_plan = plan
@@ -1070,6 +1071,12 @@ class InferenceEngine:
                 run_plan.tables_built = True
         else:
             flags = self._flags(plan) & _native.CBN_RUN_BUILD_TABLES
+        return run_plan, cols, flags
+
+    def _predict(self, plan: Plan, evidence, n_queries: int, device):
+        """predict's general path (``_general_call``)."""
+        lib = _native.load()
+        run_plan, cols, flags = self._general_call(plan, evidence, n_queries, device)
         index = torch.empty(n_queries, dtype=torch.int32, device=device)
         value = torch.empty(n_queries, dtype=torch.float32, device=device)
         row_max = torch.empty(n_queries, dtype=torch.float32, device=device)
@@ -1092,6 +1099,95 @@ class InferenceEngine:
         runs in the query kernel."""
         fp = self._fast.get((target, tuple(evidence_keys), N_max))
         return int(_native.load().cbn_plan_flags(fp.plan.handle)) if fp else 0
+
+    # ----------------------------------------------------------- posterior --
+    def posterior(self, target: str, evidence: Dict[str, torch.Tensor], N_max: int, rows: bool = True):
+        """Per query, the target's marginal normalised by its OWN sum and its
+        moments: ``(pdf or None, mass, mean, var)``, float32 tensors on the
+        device ([n_queries, N_max] and [n_queries]), in one launch with no grid
+        barrier and no batch maximum (cbn_plan_run_moments, include/cbn_amd.h).
+
+        With ``raw[q, :]`` the UNNORMALISED product row -- the row
+        ``infer_raw`` returns -- and ``s_j`` the target's sample points (this
+        call's draw when the domain is redrawn):
+        ``mass[q] = sum_j raw[q, j]``; ``pdf[q, j] = raw[q, j] / mass[q]`` (the
+        IEEE float32 quotient); ``mean[q] = (sum_j raw[q, j] s_j) / mass[q]``;
+        ``var[q] = (sum_j raw[q, j] (s_j - mean[q])**2) / mass[q]`` (centred),
+        all accumulated in float32.  A row of mass 0 (off-domain evidence)
+        follows IEEE: mass 0, pdf / mean / var NaN.  A row's outputs depend on
+        that row's evidence alone: the same evidence row gives the same bits at
+        any position of any batch on the same plan.  ``rows=False``: no
+        [n_queries, N_max] tensor is allocated or written; pdf is None.
+
+        Takes and rejects exactly the calls ``infer`` does (same plan cache,
+        redraw handling, [Q, N] column routing, conversions and errors)."""
+        return self.posterior_domain(target, evidence, N_max, rows)[:4]
+
+    def posterior_domain(self, target: str, evidence: Dict[str, torch.Tensor], N_max: int, rows: bool = True):
+        """``posterior`` plus the target domain of this call in ``infer``'s
+        shape ([n_queries or 1, N_max]): (pdf or None, mass, mean, var, domain)."""
+        plan, fp = self.call_plan(target, evidence, N_max)  # evidence=None raises AttributeError, as infer
+        device = fp.device if fp is not None else _native.require_gpu(self.bn.device)
+        try:
+            res = self._posterior_fast(fp, evidence, rows) if fp is not None else None
+            if res is None:
+                n_queries = next(iter(evidence.values())).shape[0] if len(evidence) > 0 else 1
+                res = self._posterior(plan, dict(evidence.items()), n_queries, device, rows)
+            tq = res[1].shape[0] if plan.target_observed else 1
+            return (*res, plan.target_domain.unsqueeze(0).expand(tq, -1))
+        finally:
+            if fp is None:  # a plan rebuilt per call
+                torch.cuda.current_stream(device).synchronize()
+                plan.destroy()
+
+    @staticmethod
+    def _target_points(plan: Plan, device) -> torch.Tensor:
+        """The plan's target sample points as the kernels read them: the
+        plan's own tensor when it is contiguous float32 on the device, else one
+        such copy for the call."""
+        t = plan.target_domain
+        if t.dtype is torch.float32 and t.device == device and t.is_contiguous():
+            return t
+        return t.to(device=device, dtype=torch.float32).contiguous()
+
+    def _posterior_fast(self, fp: "_FastPath", evidence, rows: bool):
+        """posterior's hot path (host_fast.run_moments: the native evidence
+        checks, the outputs, one library call); None when those checks reject
+        the evidence (conversions / the reference's errors: ``_posterior``)."""
+        plan = fp.plan
+        if fp.moments is None:
+            fn = ctypes.cast(fp.lib.cbn_plan_run_moments, ctypes.c_void_p).value
+            fp.moments = (_native.load_host().run_moments, fn, int(fp.lib.cbn_plan_moments_scratch(plan.handle, 1)))
+        host, fn, per_q = fp.moments
+        tv = self._target_points(plan, fp.device)  # (kept alive past the launch: stream-ordered free)
+        built = plan.tables_built
+        flags = self._flags(plan) & _native.CBN_RUN_BUILD_TABLES
+        res = host(fn, plan.handle.value, evidence, fp.slot_keys, fp.first, fp.device.index, plan.n_samples,
+                   plan.target_observed, tv.data_ptr(), rows, per_q, flags)
+        if res is None:  # nothing launched
+            plan.tables_built = built
+            return None
+        if type(res) is int:
+            _native.check(res, "cbn_plan_run_moments")
+        return res
+
+    def _posterior(self, plan: Plan, evidence, n_queries: int, device, rows: bool):
+        """posterior's general path (``_general_call``)."""
+        lib = _native.load()
+        run_plan, cols, flags = self._general_call(plan, evidence, n_queries, device)
+        pdf = torch.empty((n_queries, plan.n_samples), dtype=torch.float32, device=device) if rows else None
+        mass, mean, var = (torch.empty(n_queries, dtype=torch.float32, device=device) for _ in range(3))
+        ns = 0 if rows else int(lib.cbn_plan_moments_scratch(run_plan.handle, n_queries))
+        scratch = torch.empty(ns, dtype=torch.float32, device=device) if ns > 0 else None
+        tv = self._target_points(plan, device)
+        ptrs = (ctypes.c_void_p * max(1, len(cols)))(*[c.data_ptr() for c in cols])
+        with torch.cuda.device(device):
+            _native.check(lib.cbn_plan_run_moments(run_plan.handle, n_queries, ptrs, len(cols), _native.ptr(tv),
+                                                   _native.ptr(pdf) if rows else None, _native.ptr(mass),
+                                                   _native.ptr(mean), _native.ptr(var),
+                                                   _native.ptr(scratch) if scratch is not None else None, flags,
+                                                   _native.stream_ptr(device)), "cbn_plan_run_moments")
+        return pdf, mass, mean, var
 
     def timing(self):
         """(calls, avg max-pass ms, avg write-pass ms) over the timed calls of every cached plan."""

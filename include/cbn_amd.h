@@ -282,6 +282,50 @@ int64_t cbn_plan_argmax_scratch(const cbn_plan* plan, int64_t n_queries);
 int cbn_row_argmax(const float* rows, int64_t n_rows, int32_t n_cols, const float* target_values, int32_t* index,
                    float* value, float* row_max, void* stream);
 
+/* ---- posterior: per query, the marginal normalised by its OWN sum, and its
+ * moments.  No reference counterpart: bayesian_network.py:296 divides every
+ * row by one maximum over the whole batch, so a row's scale depends on the
+ * other queries of the call.  Per query row q, with raw[q, :] the
+ * UNnormalised product row (the rows of a CBN_RUN_RAW launch) and s_j =
+ * target_values[j] the target's sample points of this call:
+ *   mass[q]   = sum_j raw[q, j]                                (fp32 accumulation)
+ *   pdf[q, j] = raw[q, j] / mass[q]                            (the IEEE fp32 quotient)
+ *   mean[q]   = (sum_j raw[q, j] s_j) / mass[q]
+ *   var[q]    = (sum_j raw[q, j] (s_j - mean[q])^2) / mass[q]  (centred two-pass form)
+ * A row of mass 0 (off-domain evidence) follows IEEE: mass 0, pdf / mean / var
+ * NaN (0 / 0).  On parametric plans a NaN or inf in a row propagates by plain
+ * float arithmetic and stays in that row.  A row's four outputs depend on
+ * nothing but that row's evidence: the same evidence row gives the same bits
+ * at any position of any batch size on the same plan (bits may differ between
+ * plans of different kernel families).  All three added in ABI 5 (additive). */
+
+/* One launch on plans with CBN_PLAN_MOMENTS (the query kernel reduces each row
+ * in registers: no grid barrier, no max words; with out == NULL no [Q, N]
+ * tensor is written).  Other plans store their raw rows in `out` -- or, when
+ * out is NULL, in `scratch` (device, cbn_plan_moments_scratch floats;
+ * CBN_E_ARG when both are NULL) -- and reduce them with cbn_row_moments's
+ * kernel, which divides `out` in place.  mass is required; mean / var may be
+ * NULL (non-NULL with target_values NULL: CBN_E_ARG).  out: device [Q, N],
+ * 16-B aligned, or NULL.  flags: CBN_RUN_BUILD_TABLES only.  n_queries >= 1;
+ * evidence as cbn_plan_run.  Reports (and clears) a pending grid-barrier
+ * timeout of the plan as cbn_plan_run does. */
+int cbn_plan_run_moments(cbn_plan* plan, int64_t n_queries, const float* const* evidence, int32_t n_evidence,
+                         const float* target_values /* device [N] or NULL */, float* out /* [Q, N] or NULL */,
+                         float* mass, float* mean /* NULL ok */, float* var /* NULL ok */, float* scratch,
+                         int32_t flags, void* stream);
+
+/* Floats of scratch cbn_plan_run_moments needs for n_queries when it is called
+ * with out == NULL (0 on plans with CBN_PLAN_MOMENTS; a call that gives `out`
+ * needs none on any plan). */
+int64_t cbn_plan_moments_scratch(const cbn_plan* plan, int64_t n_queries);
+
+/* The same outputs from stored raw rows [n_rows, n_cols] (row-major float32,
+ * device); `normalize` != 0 divides each row in place by its mass.  16-B
+ * accesses when n_cols % 4 == 0 and rows is 16-B aligned.  mean / var non-NULL
+ * with target_values NULL: CBN_E_ARG. */
+int cbn_row_moments(float* rows, int64_t n_rows, int32_t n_cols, const float* target_values, int32_t normalize,
+                    float* mass, float* mean, float* var, void* stream);
+
 /* CBN_E_TIMEOUT (and clears the report) if a single-launch call of the plan
  * timed out in its grid barrier since the last report, else CBN_OK: a read of
  * the plan's host-mapped status word, no device round trip.  A caller that
@@ -302,6 +346,7 @@ int cbn_plan_check(cbn_plan* plan);
 #define CBN_PLAN_COLS 256      /* k_query_cols (evidence indexed once per slot; non-paired table plans) */
 #define CBN_PLAN_SLOTS 512     /* k_query_slots (slot-indexed evidence, global tables, >= 4 lanes per query; round 5) */
 #define CBN_PLAN_ARGMAX 1024   /* cbn_plan_run_argmax runs in the query kernel itself (no rows stored) */
+#define CBN_PLAN_MOMENTS 2048  /* cbn_plan_run_moments runs in the query kernel itself (rows stored only on request) */
 int32_t cbn_plan_flags(const cbn_plan* plan);
 
 /* Test hook: mark the plan as if a single-launch call had timed out in its
