@@ -177,6 +177,14 @@ _SIGNATURES = {
     "cbn_row_moments": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p,
                                        ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                        ctypes.c_void_p]),
+    "cbn_plan_run_quantile": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int32,
+                                             ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64,
+                                             ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                             ctypes.c_int32, ctypes.c_void_p]),
+    "cbn_plan_quantile_scratch": (ctypes.c_int64, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32]),
+    "cbn_row_quantile": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p,
+                                        ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p,
+                                        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "cbn_plan_create_param": (ctypes.c_int, [ctypes.POINTER(ParamFactor), ctypes.c_int32, ctypes.c_int32,
                                              ctypes.POINTER(ctypes.c_void_p)]),
     "cbn_param_eval": (ctypes.c_int, [ctypes.POINTER(ParamModel), ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32,
@@ -201,6 +209,8 @@ CBN_PLAN_COLS = 256
 CBN_PLAN_SLOTS = 512
 CBN_PLAN_ARGMAX = 1024
 CBN_PLAN_MOMENTS = 2048
+CBN_PLAN_QUANTILE = 4096
+CBN_MAX_QUANTILES = 16
 CBN_E_ARG = -1
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

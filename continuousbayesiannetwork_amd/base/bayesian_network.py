@@ -243,3 +243,56 @@ class BayesianNetwork:
         if not out:
             return np.zeros((0,))
         return torch.cat(out).cpu().numpy().astype(np.float64)
+
+    def quantile(self, target_node: str, evidence: Dict[str, torch.Tensor] = None, probs=(0.5,), N_max: int = 16,
+                 return_index: bool = False):
+        """The quantiles of the target's posterior per evidence row: for each
+        probability the lowest sample point of positive probability whose
+        cumulative posterior reaches it (``InferenceEngine.quantile``), in one
+        launch that stores no [n_queries, N_max] pdf.
+
+        :param evidence: {node: tensor [n_queries, 1]}, as ``infer``
+        :param probs: probabilities in [0, 1]: a sequence or tensor [P] for
+            every row, or a tensor [n_queries, P]
+        :param return_index: also return the sample points' indices (int32; -1
+            with value NaN for a row without support)
+        :return: values [n_queries, P], or (values, indices)
+        """
+        index, value, _ = self.engine.quantile(target_node, evidence, N_max, probs)
+        return (value, index) if return_index else value
+
+    def interval(self, target_node: str, evidence: Dict[str, torch.Tensor] = None, level: float = 0.95,
+                 N_max: int = 16):
+        """The central credible interval of the target per evidence row: the
+        quantiles at ``(1 - level) / 2`` and ``(1 + level) / 2``, from one call.
+
+        :return: (lo [n_queries], hi [n_queries])
+        """
+        if not 0.0 <= level <= 1.0:
+            raise ValueError("level must lie in [0, 1]")
+        value = self.quantile(target_node, evidence, ((1.0 - level) / 2.0, (1.0 + level) / 2.0), N_max)
+        return value[:, 0], value[:, 1]
+
+    def sample(self, target_node: str, evidence: Dict[str, torch.Tensor] = None, n_samples: int = 1, N_max: int = 16,
+               generator: torch.Generator = None, return_index: bool = False):
+        """Draws from the target's posterior per evidence row: ``quantile`` at
+        ``torch.rand((n_queries, n_samples), dtype=float32, device=...,
+        generator=generator)``, so a seeded generator reproduces the draws.  A
+        sample point of probability 0 is never drawn; a row without support
+        gives NaN (index -1).  ``n_samples`` up to ``CBN_MAX_QUANTILES`` (16)
+        runs inside the query kernel, more through stored rows
+        (``InferenceEngine.quantile``): at the same uniform draw the two may
+        differ by one sample point where the draw lies within float32 rounding
+        of a cdf step.
+
+        :return: values [n_queries, n_samples], or (values, indices)
+        """
+        if n_samples < 1:
+            raise ValueError("n_samples must be >= 1")
+        if evidence is None:  # (raises as infer does)
+            return self.quantile(target_node, evidence, (0.5,), N_max, return_index)
+        cols = list(evidence.values())
+        n_queries = cols[0].shape[0] if cols else 1
+        device = generator.device if generator is not None else torch.device(self.device)
+        u = torch.rand((n_queries, n_samples), device=device, dtype=torch.float32, generator=generator)
+        return self.quantile(target_node, evidence, u, N_max, return_index)

@@ -289,11 +289,26 @@ struct MomentsOut {
     float* var;
 };
 
+// Where a quantile launch's outputs go (kModeQuantile, k_row_quantile; the
+// rules: quantile_store, quant_key, quant_bad).  probs: n_probs probabilities, one [P] list for every
+// query (pstride 0) or row q's at probs + q * pstride.  index is required;
+// value (needs tv) and mass may be null.
+struct QuantileOut {
+    const float* tv;
+    const float* probs;
+    long long pstride;
+    int* index;
+    float* value;
+    float* mass;
+    int n_probs;
+};
+
 // The query kernels' last argument: the outputs of the one mode that has some
 // beyond `out` and the max words (the member the launch's MODE reads).
 union ModeOut {
     ArgmaxOut am;
     MomentsOut mo;
+    QuantileOut qu;
 };
 
 template <int CTRL>
@@ -369,6 +384,136 @@ __device__ __forceinline__ void moments_store(const float (&acc)[4 * NB], const 
         if (mo.tv && mo.mean) mo.mean[q] = mean;
         if (mo.tv && mo.var) mo.var[q] = var;
     }
+}
+
+// ---- quantile epilogue (kModeQuantile launches, k_row_quantile) ------------
+// Exclusive prefix sum over one query's L lanes (seg_sum's segments), in lane
+// order: lane l gets the sum of v over lanes [0, l) of its query, lane 0 gets
+// +0.  The values are shifted up one lane and then scanned by doubling offsets
+// (Hillis-Steele), so the association is a fixed function of l and L.  L = 2
+// and 4: quad_perm DPP steps; else a __shfl_up ladder under the l >= o guard.
+// Valid for any power of two 1 <= L <= 64; every lane of the wave must be active.
+__device__ __forceinline__ float seg_exscan(float v, int l, int L) {
+    if (L == 1) return 0.f;
+    if (L == 2) {
+        const float t = dpp_f32<0xA0>(v);  // quad_perm [0, 0, 2, 2]
+        return l ? t : 0.f;
+    }
+    if (L == 4) {
+        float t = dpp_f32<0x90>(v);  // quad_perm [0, 0, 1, 2]: one lane up
+        float s = l >= 1 ? t : 0.f;
+        t = dpp_f32<0x90>(s);
+        if (l >= 1) s = s + t;
+        t = dpp_f32<0x44>(s);  // quad_perm [0, 1, 0, 1]: two lanes up
+        if (l >= 2) s = s + t;
+        return s;
+    }
+    float s = __shfl_up(v, 1, kWave);
+    if (l < 1) s = 0.f;
+    for (int o = 1; o < L; o <<= 1) {
+        const float t = __shfl_up(s, o, kWave);
+        if (l >= o) s = s + t;
+    }
+    return s;
+}
+
+// v of the query's LAST lane (l == L - 1), in every lane of the query.
+__device__ __forceinline__ float seg_last(float v, int l, int L) {
+    if (L == 1) return v;
+    if (L == 2) return dpp_f32<0xF5>(v);  // quad_perm [1, 1, 3, 3]
+    if (L == 4) return dpp_f32<0xFF>(v);  // quad_perm [3, 3, 3, 3]
+    return __shfl(v, (int)__lane_id() - l + L - 1, kWave);
+}
+
+// One column as a candidate for a probability's quantile, for seg_max_key:
+// a column that qualifies (r > 0 and c >= t) beats every one that does not,
+// and among them the LOWEST wins (amax_key_u's order); among the others the
+// HIGHEST column of positive probability wins (the rule's fallback, which
+// catches rounding at p = 1); 0: the lane has neither.
+__device__ __forceinline__ unsigned long long quant_key(int hit, unsigned last1) {
+    return hit != INT_MAX ? amax_key_u(1u, hit) : (unsigned long long)last1;
+}
+__device__ __forceinline__ int quant_col(unsigned long long k) { return (k >> 32) ? amax_col(k) : (int)(unsigned)k - 1; }
+// a probability outside [0, 1] or NaN, or a row without a finite positive mass: index -1, value NaN
+__device__ __forceinline__ bool quant_bad(float p, float mass) {
+    return !(p >= 0.f && p <= 1.f) || !(mass > 0.f) || !(mass < INFINITY);
+}
+
+// The quantile launch's epilogue: acc[4 v + i] is the product r of column
+// colv[v] + i of query q (argmax_store's layout).  c = the inclusive prefix sum
+// of the row IN COLUMN ORDER: a scan inside each 4-column block, plus the
+// block's base from an exclusive scan over the query's lanes.  Which scan
+// depends on where the lane's blocks lie, judged by COLUMN NUMBER (the paired
+// layouts swap colv[0] and colv[1] with the query slot's parity):
+//   one block, or two adjacent ones (unpaired, col = (l VPL + v) 4): the lane
+//     owns 4 NB contiguous columns; base = exscan of the lane totals, the upper
+//     block adds the lower block's total;
+//   two blocks N / 2 apart (paired): the lower block's base is the exscan of the
+//     lower totals, the upper block's is ALL lower totals plus the exscan of
+//     the upper totals.
+// mass = c of the row's last column.  Then per probability p (kernel-uniform
+// count): t = p * mass, each lane's lowest column with r > 0 and c >= t (else
+// its highest with r > 0) as a key, one seg_max_key, and lane l == 0 stores.
+// The arithmetic is a function of the columns' values and numbers alone, so a
+// row's bits do not depend on its slot or batch.  Called by every lane of the
+// wave (`valid`: the lane holds a query of the batch).
+template <int NB>
+__device__ __forceinline__ void quantile_store(const float (&acc)[4 * NB], const int (&colv)[NB], int l, int L, bool valid,
+                                               long long q, const QuantileOut& qu) {
+    static_assert(NB <= 2, "more than two blocks per lane: no layout has them");
+    float c[4 * NB], base[NB];
+#pragma unroll
+    for (int v = 0; v < NB; ++v) {
+        c[4 * v] = acc[4 * v];
+#pragma unroll
+        for (int i = 1; i < 4; ++i) c[4 * v + i] = c[4 * v + i - 1] + acc[4 * v + i];
+    }
+    bool sw = false;  // the lane's upper columns are in register block 0
+    if (NB == 1) {
+        base[0] = seg_exscan(c[3], l, L);
+    } else {
+        sw = colv[0] > colv[NB - 1];
+        const float tlo = sw ? c[4 * NB - 1] : c[3], thi = sw ? c[3] : c[4 * NB - 1];
+        const int gap = sw ? colv[0] - colv[NB - 1] : colv[NB - 1] - colv[0];
+        float blo, bhi;
+        if (gap == 4) {  // (the same in every lane of the launch)
+            blo = seg_exscan(tlo + thi, l, L);
+            bhi = blo + tlo;
+        } else {
+            blo = seg_exscan(tlo, l, L);
+            bhi = seg_last(blo + tlo, l, L) + seg_exscan(thi, l, L);
+        }
+        base[0] = sw ? bhi : blo;
+        base[NB - 1] = sw ? blo : bhi;
+    }
+    unsigned last1 = 0;  // 1 + the lane's highest column with r > 0
+#pragma unroll
+    for (int v = 0; v < NB; ++v)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            c[4 * v + i] = base[v] + c[4 * v + i];
+            if (acc[4 * v + i] > 0.f) last1 = max(last1, (unsigned)(colv[v] + i + 1));
+        }
+    const float mass = seg_last(sw ? c[3] : c[4 * NB - 1], l, L);
+    const int P = qu.n_probs;
+    const float* pr = qu.probs + (valid ? q * qu.pstride : 0);
+    for (int j = 0; j < P; ++j) {  // kernel-uniform
+        const float p = qu.pstride == 0 ? qu.probs[j] : pr[j];  // (one list: a uniform load)
+        const float t = p * mass;
+        int hit = INT_MAX;
+#pragma unroll
+        for (int v = 0; v < NB; ++v)
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+                if (acc[4 * v + i] > 0.f && c[4 * v + i] >= t) hit = min(hit, colv[v] + i);
+        const unsigned long long k = seg_max_key(quant_key(hit, last1), l, L);
+        if (valid && l == 0) {
+            const int idx = quant_bad(p, mass) ? -1 : quant_col(k);
+            qu.index[q * P + j] = idx;
+            if (qu.value && qu.tv) qu.value[q * P + j] = idx >= 0 ? qu.tv[idx] : __uint_as_float(0x7FC00000u);
+        }
+    }
+    if (valid && l == 0 && qu.mass) qu.mass[q] = mass;
 }
 
 // Diagnostic build only (-DCBN_STAMPS): per-wave s_memtime stamps of the query
@@ -891,7 +1036,11 @@ constexpr int kLoc = 8;
 // MODE 5 (moments): launched like the raw mode too; each query's row is reduced
 // to (mass, mean, var) and, when `out` is given, stored divided by its OWN sum
 // (moments_store).  Rows are independent of each other: no max words either.
-constexpr int kModeMax = 0, kModeWrite = 1, kModeFused = 2, kModeRaw = 3, kModeArgmax = 4, kModeMoments = 5;
+// MODE 6 (quantile): launched like the arg-max mode; each query's row is scanned
+// in column order and searched once per probability (quantile_store): no rows,
+// no max words.
+constexpr int kModeMax = 0, kModeWrite = 1, kModeFused = 2, kModeRaw = 3, kModeArgmax = 4, kModeMoments = 5,
+              kModeQuantile = 6;
 constexpr unsigned kSpinLimit = 1u << 22;  // bounded barrier spin (~0.3 s): never hang
 
 // Fused grid barrier on the global max, called by ONE wave per block (all
@@ -976,6 +1125,7 @@ __device__ __forceinline__ unsigned slot_barrier_max(unsigned* __restrict__ sync
 //   kModeRaw     the unnormalised rows and the per-block maxima (a scale pass divides)
 //   kModeArgmax  per query the first column of the row maximum (ArgmaxOut), no rows
 //   kModeMoments per query mass / mean / var (MomentsOut) and, with `out`, the row / its own sum
+//   kModeQuantile per query and probability the inverse cdf's column (QuantileOut), no rows
 // What a mode does with a lane's products is the same in every kernel and lives
 // here.  lane / wid / tid / nthr are the caller's own values (k_query_fast
 // reads blockDim, the others know it at compile time).
@@ -1021,6 +1171,7 @@ __device__ __forceinline__ void round_epilogue(const float (&acc)[4 * VPL], cons
                                                bool hold, long long& fq, const ModeOut& mx) {
     if (MODE == kModeArgmax) argmax_store<VPL>(acc, col, l, L, valid, q, mx.am);
     if (MODE == kModeMoments) moments_store<VPL>(acc, col, l, L, valid, ok, q, N, out, mx.mo);
+    if (MODE == kModeQuantile) quantile_store<VPL>(acc, col, l, L, valid, q, mx.qu);
     if (ok) {
         if (MODE == kModeFused && hold) fq = q;
         if (MODE == kModeWrite) {
@@ -1029,7 +1180,7 @@ __device__ __forceinline__ void round_epilogue(const float (&acc)[4 * VPL], cons
             store_row<VPL>(out + q * N, col, acc);
 #pragma unroll
             for (int i = 0; i < 4 * VPL; ++i) lmax = fmaxf(lmax, acc[i]);
-        } else if (MODE != kModeArgmax && MODE != kModeMoments) {
+        } else if (MODE != kModeArgmax && MODE != kModeMoments && MODE != kModeQuantile) {
 #pragma unroll
             for (int i = 0; i < 4 * VPL; ++i) lmax = fmaxf(lmax, acc[i]);
         }
@@ -2305,6 +2456,10 @@ k_query_staged(const float* __restrict__ gimage, int image_floats, int rec_off, 
             const int colv[2] = {clo, chi};
             moments_store<2>(acc, colv, l, 4, q < q1, q < q1, q, N, out, mx.mo);
         }
+        if (MODE == kModeQuantile) {  // (a scan in column order: quantile_store tells clo from chi by number)
+            const int colv[2] = {clo, chi};
+            quantile_store<2>(acc, colv, l, 4, q < q1, q, mx.qu);
+        }
         if (q < q1) {
             if (MODE == kModeFused) fq = q;
             if (MODE == kModeRaw && wt_raw) {
@@ -2322,7 +2477,7 @@ k_query_staged(const float* __restrict__ gimage, int image_floats, int rec_off, 
                     ? make_float4(acc[4] / dv, acc[5] / dv, acc[6] / dv, acc[7] / dv)
                     : make_float4(acc[4], acc[5], acc[6], acc[7]);
             }
-            if (MODE != kModeWrite && MODE != kModeArgmax && MODE != kModeMoments)
+            if (MODE != kModeWrite && MODE != kModeArgmax && MODE != kModeMoments && MODE != kModeQuantile)
 #pragma unroll
                 for (int i = 0; i < 8; ++i) lmax = fmaxf(lmax, acc[i]);
         }
@@ -2618,6 +2773,87 @@ k_row_moments(float* rows, long long n_rows, int n_cols, int LR, int normalize, 
     }
 }
 
+// QuantileOut of stored raw rows [n_rows, n_cols]: the quantiles of every plan
+// without the epilogue in its query kernel, and of any call with more than
+// CBN_MAX_QUANTILES probabilities.  LR lanes hold a row (a power of two <= 64,
+// 64 / LR rows per wave), and walk it in tiles of 4 LR columns: lane l owns the
+// columns 4 l .. 4 l + 3 of the tile (0 past the row's end: x + 0 = x), scans
+// them, takes its base from the carry of the tiles before plus an exclusive
+// scan of the tile's lane totals, and the tile's last prefix sum is the next
+// carry -- the same fixed association on every pass, so a pass that rescans
+// the row meets the same bits.  Pass 1 gives the mass and each lane's highest
+// column of positive probability; then per probability the lowest qualifying
+// column, from the registers when the row is one tile, else by a rescan.  Plain
+// float compares: a NaN or inf in a parametric row makes the mass non-finite
+// (index -1, quant_bad), a -0 or NaN entry is never a quantile.  VEC: 16-B loads
+// (n_cols % 4 == 0, aligned rows).
+template <bool VEC>
+__global__ void __launch_bounds__(kRowThreads)
+k_row_quantile(const float* __restrict__ rows, long long n_rows, int n_cols, int LR, QuantileOut qu) {
+    const int l = (int)(threadIdx.x & (unsigned)(LR - 1));
+    const long long rpb = kRowThreads / LR;
+    const int tile = 4 * LR, nt = (n_cols + tile - 1) / tile;
+    const int P = qu.n_probs;
+    // (block-uniform trip counts throughout: every lane stays active for the cross-lane steps)
+    for (long long r0 = (long long)blockIdx.x * rpb; r0 < n_rows; r0 += (long long)gridDim.x * rpb) {
+        const long long rr = r0 + threadIdx.x / LR;
+        const bool valid = rr < n_rows;
+        const long long r = valid ? rr : n_rows - 1;
+        const float* row = rows + r * n_cols;
+        float a[4], c[4], carry = 0.f;
+        auto scan_tile = [&](int t) {
+            const int c0 = t * tile + 4 * l;
+            if (VEC) {
+                const float4 x = c0 < n_cols ? *reinterpret_cast<const float4*>(row + c0) : make_float4(0.f, 0.f, 0.f, 0.f);
+                a[0] = x.x, a[1] = x.y, a[2] = x.z, a[3] = x.w;
+            } else {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) a[i] = c0 + i < n_cols ? row[c0 + i] : 0.f;
+            }
+            c[0] = a[0];
+#pragma unroll
+            for (int i = 1; i < 4; ++i) c[i] = c[i - 1] + a[i];
+            const float base = carry + seg_exscan(c[3], l, LR);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) c[i] = base + c[i];
+            carry = seg_last(c[3], l, LR);
+            return c0;
+        };
+        unsigned last1 = 0;
+        for (int t = 0; t < nt; ++t) {
+            const int c0 = scan_tile(t);
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+                if (a[i] > 0.f) last1 = max(last1, (unsigned)(c0 + i + 1));  // (a padding column is 0)
+        }
+        const float mass = carry;
+        const float* pr = qu.probs + r * qu.pstride;
+        for (int j = 0; j < P; ++j) {
+            const float p = pr[j];
+            const float th = p * mass;
+            int hit = INT_MAX;
+            auto search = [&](int c0) {
+#pragma unroll
+                for (int i = 3; i >= 0; --i)
+                    if (a[i] > 0.f && c[i] >= th) hit = min(hit, c0 + i);
+            };
+            if (nt == 1) {
+                search(4 * l);
+            } else {
+                carry = 0.f;
+                for (int t = 0; t < nt; ++t) search(scan_tile(t));
+            }
+            const unsigned long long k = seg_max_key(quant_key(hit, last1), l, LR);
+            if (valid && l == 0) {
+                const int idx = quant_bad(p, mass) ? -1 : quant_col(k);
+                qu.index[r * P + j] = idx;
+                if (qu.value && qu.tv) qu.value[r * P + j] = idx >= 0 ? qu.tv[idx] : __uint_as_float(0x7FC00000u);
+            }
+        }
+        if (valid && l == 0 && qu.mass) qu.mass[r] = mass;
+    }
+}
+
 int g_num_cu = 0;
 
 }  // namespace
@@ -2653,6 +2889,21 @@ static int launch_row_moments(float* rows, long long n_rows, int n_cols, bool no
     else
         hipLaunchKernelGGL(k_row_moments<false>, dim3((unsigned)blocks), dim3(kRowThreads), 0, s, rows, n_rows, n_cols, LR,
                            normalize ? 1 : 0, mo);
+    HIP_TRY(hipGetLastError());
+    return CBN_OK;
+}
+
+// the quantiles of rows [n_rows, n_cols] on `s` (k_row_quantile)
+static int launch_row_quantile(const float* rows, long long n_rows, int n_cols, const QuantileOut& qu, hipStream_t s) {
+    const bool vec = n_cols % 4 == 0 && reinterpret_cast<uintptr_t>(rows) % 16 == 0;
+    int LR = 1;
+    while (4 * LR < n_cols && LR < kWave) LR <<= 1;
+    const long long rpb = kRowThreads / LR;
+    const long long blocks = std::max(1LL, std::min((n_rows + rpb - 1) / rpb, (long long)num_cu() * 16));
+    if (vec)
+        hipLaunchKernelGGL(k_row_quantile<true>, dim3((unsigned)blocks), dim3(kRowThreads), 0, s, rows, n_rows, n_cols, LR, qu);
+    else
+        hipLaunchKernelGGL(k_row_quantile<false>, dim3((unsigned)blocks), dim3(kRowThreads), 0, s, rows, n_rows, n_cols, LR, qu);
     HIP_TRY(hipGetLastError());
     return CBN_OK;
 }
@@ -2738,7 +2989,7 @@ template <int VPL, bool LDS, int MODE>
 void launch_fast_k(const cbn_plan* p, unsigned blocks, hipStream_t s, const EvPtrs& ev, long long Q, int L,
                    unsigned epoch, const unsigned* max_in, int n_max, unsigned* max_out, float* out,
                    const FoldJob* fold = nullptr, const ModeOut* mxp = nullptr) {
-    ModeOut mx;  // (read by kModeArgmax / kModeMoments only)
+    ModeOut mx;  // (read by kModeArgmax / kModeMoments / kModeQuantile only)
     memset(&mx, 0, sizeof(mx));
     if (mxp) mx = *mxp;
     if (p->staged) {  // paired N = 32 layout in LDS: the staged kernel (same grid, same words)
@@ -2850,13 +3101,15 @@ unsigned query_blocks(const cbn_plan* p, long long Q, int L, bool reserve) {
 //                `fold`: an earlier step's rows to scale on the way (staged plans)
 //   kModeArgmax  `mx->am` only: the raw launch's grid and rounds, no rows, no max words
 //   kModeMoments `mx->mo`, and out = products / the row's own sum when non-null: launched as kModeArgmax
+//   kModeQuantile `mx->qu` only: launched as kModeArgmax
 template <int MODE>
 int launch_mode(cbn_plan* p, long long Q, const EvPtrs& ev, const unsigned* max_in, int n_max, unsigned* max_out,
                 float* out, hipStream_t s, const FoldJob* fold = nullptr, const ModeOut* mx = nullptr) {
     if (MODE == kModeMax || MODE == kModeRaw) n_max = p->max_slots;
     with_variant(p, [&](auto vpl, auto lds) {
         const int L = p->N / (4 * vpl.value);
-        const unsigned blocks = query_blocks(p, Q, L, MODE == kModeRaw || MODE == kModeArgmax || MODE == kModeMoments);
+        const unsigned blocks =
+            query_blocks(p, Q, L, MODE == kModeRaw || MODE == kModeArgmax || MODE == kModeMoments || MODE == kModeQuantile);
         launch_fast_k<vpl.value, lds.value, MODE>(p, blocks, s, ev, Q, L, 0u, max_in, n_max, max_out, out, fold, mx);
     });
     HIP_TRY(hipGetLastError());
@@ -2985,6 +3238,8 @@ void allow_lds(size_t bytes) {
         allow_fast_lds<2, LDS, kModeArgmax>((int)bytes);
         allow_fast_lds<1, LDS, kModeMoments>((int)bytes);
         allow_fast_lds<2, LDS, kModeMoments>((int)bytes);
+        allow_fast_lds<1, LDS, kModeQuantile>((int)bytes);
+        allow_fast_lds<2, LDS, kModeQuantile>((int)bytes);
     }
 }
 
@@ -2992,6 +3247,8 @@ void allow_lds(size_t bytes) {
 bool argmax_native(const cbn_plan* p) { return p->fast && !p->param && !p->direct; }
 // ... and so do its moments (kModeMoments): the same plans
 bool moments_native(const cbn_plan* p) { return argmax_native(p); }
+// ... and its quantiles (kModeQuantile), for up to CBN_MAX_QUANTILES probabilities per query
+bool quantile_native(const cbn_plan* p) { return argmax_native(p); }
 
 // Rows of a factor's table: the product of its observed parents' cards
 // (clamped, so a sum over the factors cannot overflow).
@@ -3459,7 +3716,8 @@ int cbn_plan_create(const cbn_factor_desc* factors, int32_t n_factors, int32_t n
                                        reinterpret_cast<const void*>(&k_query_staged<kModeFused>),
                                        reinterpret_cast<const void*>(&k_query_staged<kModeRaw>),
                                        reinterpret_cast<const void*>(&k_query_staged<kModeArgmax>),
-                                       reinterpret_cast<const void*>(&k_query_staged<kModeMoments>)})
+                                       reinterpret_cast<const void*>(&k_query_staged<kModeMoments>),
+                                       reinterpret_cast<const void*>(&k_query_staged<kModeQuantile>)})
                     (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBudget);
             }
             P->fast_lds_bytes =
@@ -3850,6 +4108,71 @@ int cbn_plan_run_moments(cbn_plan* plan, int64_t n_queries, const float* const* 
     return launch_mode<kModeMoments>(plan, n_queries, ev, nullptr, 0, nullptr, out, s, nullptr, &mx);
 }
 
+static bool quantile_args_ok(const float* probs, int32_t n_probs, int64_t probs_stride, const int32_t* index) {
+    return probs && index && n_probs >= 1 && (probs_stride == 0 || probs_stride >= n_probs);
+}
+
+int cbn_row_quantile(const float* rows, int64_t n_rows, int32_t n_cols, const float* target_values, const float* probs,
+                     int32_t n_probs, int64_t probs_stride, int32_t* index, float* value, float* mass, void* stream) {
+    if (n_rows < 0 || n_cols < 1 || (n_rows > 0 && !rows) || !quantile_args_ok(probs, n_probs, probs_stride, index))
+        return set_err(CBN_E_ARG, "cbn_row_quantile: bad arguments");
+    if (n_rows == 0) return CBN_OK;
+    const QuantileOut qu = {target_values, probs, (long long)probs_stride, index, value, mass, (int)n_probs};
+    return launch_row_quantile(rows, (long long)n_rows, (int)n_cols, qu, reinterpret_cast<hipStream_t>(stream));
+}
+
+int64_t cbn_plan_quantile_scratch(const cbn_plan* plan, int64_t n_queries, int32_t n_probs) {
+    if (!plan || n_queries < 0 || (quantile_native(plan) && n_probs <= CBN_MAX_QUANTILES)) return 0;
+    return n_queries * (int64_t)plan->N;
+}
+
+int cbn_plan_run_quantile(cbn_plan* plan, int64_t n_queries, const float* const* evidence, int32_t n_evidence,
+                          const float* target_values, const float* probs, int32_t n_probs, int64_t probs_stride,
+                          int32_t* index, float* value, float* mass, float* scratch, int32_t flags, void* stream) {
+    if (!plan) return set_err(CBN_E_ARG, "null plan");
+    if (!index || !probs) return set_err(CBN_E_ARG, "cbn_plan_run_quantile: null probabilities or output");
+    if (n_probs < 1) return set_err(CBN_E_ARG, "cbn_plan_run_quantile: needs >= 1 probability");
+    if (probs_stride != 0 && probs_stride < n_probs)
+        return set_err(CBN_E_ARG, "cbn_plan_run_quantile: probs_stride must be 0 or >= n_probs");
+    if (n_queries <= 0) return set_err(CBN_E_ARG, "cbn_plan_run_quantile: needs >= 1 query");
+    if (n_evidence < 0 || (n_evidence > 0 && !evidence)) return set_err(CBN_E_ARG, "cbn_plan_run_quantile: null evidence");
+    for (int i = 0; i < n_evidence; ++i)
+        if (!evidence[i]) return set_err(CBN_E_ARG, "null evidence column %d", i);
+    const bool native = quantile_native(plan) && n_probs <= CBN_MAX_QUANTILES;
+    if (!native && !scratch)
+        return set_err(CBN_E_ARG, "cbn_plan_run_quantile: this call needs cbn_plan_quantile_scratch floats of scratch");
+    if (!native && reinterpret_cast<uintptr_t>(scratch) % 16)
+        return set_err(CBN_E_ARG, "cbn_plan_run_quantile: scratch must be 16-B aligned");
+    const bool table = !plan->param && !plan->direct;
+    if (table) {
+        if (n_evidence != plan->ns) return set_err(CBN_E_ARG, "plan expects %d evidence columns, got %d", plan->ns, n_evidence);
+        if (!plan->d_fac || !plan->d_slots || !plan->d_image || !plan->d_sync)
+            return set_err(CBN_E_ARG, "plan has no device buffers");
+    }
+    CBN_TRY(take_pending_timeout(plan));
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const QuantileOut qu = {target_values, probs, (long long)probs_stride, index, value, mass, (int)n_probs};
+    if (!table || (plan->fast && !native)) {
+        // direct / parametric plans, and a fast table plan asked for more probabilities than its kernel
+        // serves: their raw launch (per-block maxima into the plan's own words, unused here)
+        CBN_TRY(cbn_plan_run(plan, n_queries, evidence, n_evidence, plan->d_sync + kMaxWordOff, scratch,
+                             (flags & CBN_RUN_BUILD_TABLES) | CBN_RUN_RAW, stream));
+        return launch_row_quantile(scratch, (long long)n_queries, plan->N, qu, s);
+    }
+    if (flags & CBN_RUN_BUILD_TABLES) CBN_TRY(cbn_plan_build_tables(plan, stream));
+    if (!native) {
+        // generic table plans: the write pass dividing by 1.0f stores the raw rows (IEEE x / 1 = x)
+        CBN_TRY(cbn_plan_query_write(plan, n_queries, evidence, n_evidence, plan->d_sync + kOneWordOff, scratch, stream));
+        return launch_row_quantile(scratch, (long long)n_queries, plan->N, qu, s);
+    }
+    EvPtrs ev;
+    CBN_TRY(pack_evidence(plan, evidence, n_evidence, n_queries, ev));
+    ModeOut mx;
+    memset(&mx, 0, sizeof(mx));
+    mx.qu = qu;
+    return launch_mode<kModeQuantile>(plan, n_queries, ev, nullptr, 0, nullptr, nullptr, s, nullptr, &mx);
+}
+
 int cbn_plan_status(cbn_plan* plan, int32_t* status) {
     if (!plan || !status) return set_err(CBN_E_ARG, "cbn_plan_status: bad arguments");
     unsigned v = 0;
@@ -3878,7 +4201,8 @@ int32_t cbn_plan_flags(const cbn_plan* plan) {
            (plan->fused_ok ? CBN_PLAN_FUSED : 0) | (plan->param ? CBN_PLAN_PARAMETRIC : 0) |
            (plan->vpl == 2 ? CBN_PLAN_VPL2 : 0) | (plan->direct ? CBN_PLAN_DIRECT : 0) |
            (plan->cols ? CBN_PLAN_COLS : 0) | (plan->slots ? CBN_PLAN_SLOTS : 0) |
-           (argmax_native(plan) ? CBN_PLAN_ARGMAX : 0) | (moments_native(plan) ? CBN_PLAN_MOMENTS : 0);
+           (argmax_native(plan) ? CBN_PLAN_ARGMAX : 0) | (moments_native(plan) ? CBN_PLAN_MOMENTS : 0) |
+           (quantile_native(plan) ? CBN_PLAN_QUANTILE : 0);
 }
 
 int32_t cbn_plan_max_words(const cbn_plan* plan) {

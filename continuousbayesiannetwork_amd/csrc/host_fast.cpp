@@ -193,6 +193,46 @@ py::object run_moments(uintptr_t fn, uintptr_t plan, py::dict evidence, py::tupl
     return py::make_tuple(pdf.defined() ? py::cast(pdf) : py::object(py::none()), mass, mean, var);
 }
 
+// InferenceEngine.quantile's hot path, run_moments's sibling: run's evidence
+// checks, then index (int32 [Q, P]), value (float32 [Q, P]) and mass (float32
+// [Q]) -- plus `scratch_per_query` floats of scratch per query when the query
+// kernel does not serve the call (cbn_plan_quantile_scratch) -- and ONE call of
+// cbn_plan_run_quantile (passed in as `fn`) on the current stream.  probs: a
+// contiguous float32 tensor on the device, [P] for every query or [Q, P].
+// Returns (index, value, mass); None when a fast check failed; an int = the C
+// ABI's error code.
+using quantile_fn = int (*)(void*, int64_t, const float* const*, int32_t, const float*, const float*, int32_t, int64_t,
+                            int32_t*, float*, float*, float*, int32_t, hipStream_t);
+
+py::object run_quantile(uintptr_t fn, uintptr_t plan, py::dict evidence, py::tuple slots, py::object first,
+                        int64_t device_index, bool target_observed, uintptr_t tv_ptr, py::object probs_obj,
+                        int64_t scratch_per_query, int32_t flags) {
+    Cols c;
+    if (!gather(evidence, slots, first, device_index, target_observed, c)) return py::none();
+    if (!THPVariable_Check(probs_obj.ptr())) return py::none();
+    const at::Tensor& pt = THPVariable_Unpack(probs_obj.ptr());
+    if (pt.scalar_type() != at::kFloat || !pt.is_cuda() || pt.get_device() != device_index || !pt.is_contiguous() ||
+        pt.dim() < 1 || pt.dim() > 2 || pt.size(-1) < 1 || (pt.dim() == 2 && pt.size(0) != c.n))
+        return py::none();
+    const int64_t P = pt.size(-1);
+    const auto dev = at::Device(at::kCUDA, (c10::DeviceIndex)device_index);
+    const auto fopt = at::TensorOptions().dtype(at::kFloat).device(dev);
+    at::Tensor index = at::empty({c.n, P}, at::TensorOptions().dtype(at::kInt).device(dev));
+    at::Tensor value = at::empty({c.n, P}, fopt);
+    at::Tensor mass = at::empty({c.n}, fopt);
+    at::Tensor scratch;  // (freed at return: stream-ordered behind the launches that use it)
+    if (scratch_per_query > 0) scratch = at::empty({c.n * scratch_per_query}, fopt);
+    const hipStream_t s = c10::hip::getCurrentHIPStream(device_index).stream();
+    const int rc = reinterpret_cast<quantile_fn>(fn)(
+        reinterpret_cast<void*>(plan), c.n, c.p, (int32_t)PyTuple_GET_SIZE(slots.ptr()),
+        reinterpret_cast<const float*>(tv_ptr), static_cast<const float*>(pt.data_ptr()), (int32_t)P,
+        pt.dim() == 2 ? P : 0, static_cast<int32_t*>(index.data_ptr()), static_cast<float*>(value.data_ptr()),
+        static_cast<float*>(mass.data_ptr()), scratch.defined() ? static_cast<float*>(scratch.data_ptr()) : nullptr,
+        flags, s);
+    if (rc) return py::int_(rc);
+    return py::make_tuple(index, value, mass);
+}
+
 using scale_fn = int (*)(float*, int64_t, const unsigned*, int32_t, hipStream_t);
 using scale_batch_fn = int (*)(float* const*, const int64_t*, int32_t, const unsigned*, int32_t, hipStream_t);
 
@@ -1255,6 +1295,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("run", &run);
     m.def("run_argmax", &run_argmax);
     m.def("run_moments", &run_moments);
+    m.def("run_quantile", &run_quantile);
     m.def("scale", &scale);
     m.def("nccl_unique_id", &nccl_unique_id);
     m.def("nccl_comm_init", &nccl_comm_init);

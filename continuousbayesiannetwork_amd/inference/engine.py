@@ -215,7 +215,7 @@ class _FastPath:
     """Everything the hot path needs for one cached (target, evidence keys, N)."""
 
     __slots__ = ("plan", "device", "first", "ptrs", "max_ptr", "lib", "tdom", "host", "run_fn", "slot_keys",
-                 "scale_fn", "host_scale", "words", "redraw", "runner", "argmax", "moments")
+                 "scale_fn", "host_scale", "words", "redraw", "runner", "argmax", "moments", "quantile")
 
     def __init__(self, plan: "Plan", device: torch.device, first_key):
         self.plan = plan
@@ -237,6 +237,8 @@ class _FastPath:
         self.runner = None  # native Runner of this fast path (InferenceEngine._runner), built on first use
         self.argmax = None  # predict: (host_fast.run_argmax, cbn_plan_run_argmax, scratch floats per query)
         self.moments = None  # posterior: (host_fast.run_moments, cbn_plan_run_moments, scratch floats per query)
+        # quantile: (host_fast.run_quantile, cbn_plan_run_quantile, scratch floats per query at P <= / > CBN_MAX_QUANTILES)
+        self.quantile = None
 
 
 class InferenceEngine:
@@ -1188,6 +1190,114 @@ class InferenceEngine:
                                                    _native.ptr(scratch) if scratch is not None else None, flags,
                                                    _native.stream_ptr(device)), "cbn_plan_run_moments")
         return pdf, mass, mean, var
+
+    # ------------------------------------------------------------ quantile --
+    @staticmethod
+    def _probs(probs, device) -> torch.Tensor:
+        """``quantile``'s probabilities as the kernels read them: a contiguous
+        float32 tensor [P] or [Q, P] on the device.  A host sequence or CPU
+        tensor is range-checked here (ValueError for NaN or a value outside
+        [0, 1]); a device tensor is not (no sync: the kernel's -1 / NaN rule
+        applies to a bad entry)."""
+        if not isinstance(probs, torch.Tensor):
+            probs = torch.as_tensor(probs, dtype=torch.float32)
+        if probs.dim() == 0:
+            probs = probs.reshape(1)
+        if probs.dim() > 2 or probs.shape[-1] < 1:
+            raise ValueError(f"probs must be [P] or [n_queries, P] with P >= 1, got shape {tuple(probs.shape)}")
+        if not probs.is_floating_point():
+            probs = probs.to(torch.float32)
+        if probs.device.type == "cpu" and not bool(((probs >= 0) & (probs <= 1)).all()):
+            raise ValueError("probs must lie in [0, 1]")
+        if probs.device != device or probs.dtype is not torch.float32 or not probs.is_contiguous():
+            probs = probs.to(device=device, dtype=torch.float32).contiguous()
+        return probs
+
+    def quantile(self, target: str, evidence: Dict[str, torch.Tensor], N_max: int, probs):
+        """Per query and probability, the inverse cdf of the target's marginal:
+        ``(index int32 [n_queries, P], value float32 [n_queries, P], mass
+        float32 [n_queries])`` on the device, in one launch that stores no
+        [n_queries, N_max] tensor (cbn_plan_run_quantile, include/cbn_amd.h).
+
+        ``probs``: a sequence or 1-D tensor [P] shared by every query, or a
+        float tensor [n_queries, P].  With ``r`` the UNNORMALISED product row
+        (the row ``infer_raw`` returns), ``c`` its float32 inclusive prefix sum
+        and ``mass = c[-1]``: ``index[q, k]`` is the lowest column with
+        ``r > 0`` and ``c >= probs[k] * mass`` (the highest column with
+        ``r > 0`` when rounding leaves none), ``value = target_domain[index]``
+        (this call's draw when the domain is redrawn).  No probability returns
+        a column of probability 0; ``index`` is non-decreasing in the
+        probability.  A row of mass 0 (off-domain evidence) gives -1 / NaN, and
+        so does an entry whose probability (of a device tensor) is NaN or
+        outside [0, 1].  A row's outputs depend on that row's evidence and
+        probabilities alone.  More than ``CBN_MAX_QUANTILES`` probabilities,
+        and plans without the in-kernel scan, store the raw rows in scratch and
+        scan them with a second kernel, which associates the float32 prefix
+        sum differently: on an entry whose ``probs[k] * mass`` lies within
+        rounding of a cdf step, a call with 16 probabilities and one with 17
+        may return neighbouring columns of positive probability.
+
+        Takes and rejects exactly the calls ``infer`` does (same plan cache,
+        redraw handling, [Q, N] column routing, conversions and errors)."""
+        plan, fp = self.call_plan(target, evidence, N_max)  # evidence=None raises AttributeError, as infer
+        device = fp.device if fp is not None else _native.require_gpu(self.bn.device)
+        try:
+            pt = self._probs(probs, device)
+            res = self._quantile_fast(fp, evidence, pt) if fp is not None else None
+            if res is None:
+                n_queries = next(iter(evidence.values())).shape[0] if len(evidence) > 0 else 1
+                res = self._quantile(plan, dict(evidence.items()), n_queries, device, pt)
+            return res
+        finally:
+            if fp is None:  # a plan rebuilt per call
+                torch.cuda.current_stream(device).synchronize()
+                plan.destroy()
+
+    def _quantile_fast(self, fp: "_FastPath", evidence, probs: torch.Tensor):
+        """quantile's hot path (host_fast.run_quantile: the native evidence
+        checks, the outputs, one library call); None when those checks reject
+        the evidence (conversions / the reference's errors: ``_quantile``)."""
+        plan = fp.plan
+        if fp.quantile is None:
+            fn = ctypes.cast(fp.lib.cbn_plan_run_quantile, ctypes.c_void_p).value
+            fp.quantile = (_native.load_host().run_quantile, fn,
+                           int(fp.lib.cbn_plan_quantile_scratch(plan.handle, 1, 1)),
+                           int(fp.lib.cbn_plan_quantile_scratch(plan.handle, 1, _native.CBN_MAX_QUANTILES + 1)))
+        host, fn, per_q, per_q_many = fp.quantile
+        tv = self._target_points(plan, fp.device)  # (kept alive past the launch: stream-ordered free)
+        built = plan.tables_built
+        flags = self._flags(plan) & _native.CBN_RUN_BUILD_TABLES
+        res = host(fn, plan.handle.value, evidence, fp.slot_keys, fp.first, fp.device.index, plan.target_observed,
+                   tv.data_ptr(), probs, per_q if probs.shape[-1] <= _native.CBN_MAX_QUANTILES else per_q_many, flags)
+        if res is None:  # nothing launched
+            plan.tables_built = built
+            return None
+        if type(res) is int:
+            _native.check(res, "cbn_plan_run_quantile")
+        return res
+
+    def _quantile(self, plan: Plan, evidence, n_queries: int, device, probs: torch.Tensor):
+        """quantile's general path (``_general_call``)."""
+        lib = _native.load()
+        # (before _general_call, which marks the plan's tables as built: nothing is launched on this raise)
+        if probs.dim() == 2 and probs.shape[0] != n_queries:
+            raise ValueError(f"probs has {probs.shape[0]} rows for {n_queries} queries")
+        run_plan, cols, flags = self._general_call(plan, evidence, n_queries, device)
+        P = probs.shape[-1]
+        index = torch.empty((n_queries, P), dtype=torch.int32, device=device)
+        value = torch.empty((n_queries, P), dtype=torch.float32, device=device)
+        mass = torch.empty(n_queries, dtype=torch.float32, device=device)
+        ns = int(lib.cbn_plan_quantile_scratch(run_plan.handle, n_queries, P))
+        scratch = torch.empty(ns, dtype=torch.float32, device=device) if ns > 0 else None
+        tv = self._target_points(plan, device)
+        ptrs = (ctypes.c_void_p * max(1, len(cols)))(*[c.data_ptr() for c in cols])
+        with torch.cuda.device(device):
+            _native.check(lib.cbn_plan_run_quantile(run_plan.handle, n_queries, ptrs, len(cols), _native.ptr(tv),
+                                                    _native.ptr(probs), P, P if probs.dim() == 2 else 0,
+                                                    _native.ptr(index), _native.ptr(value), _native.ptr(mass),
+                                                    _native.ptr(scratch) if scratch is not None else None, flags,
+                                                    _native.stream_ptr(device)), "cbn_plan_run_quantile")
+        return index, value, mass
 
     def timing(self):
         """(calls, avg max-pass ms, avg write-pass ms) over the timed calls of every cached plan."""

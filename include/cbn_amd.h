@@ -326,6 +326,67 @@ int64_t cbn_plan_moments_scratch(const cbn_plan* plan, int64_t n_queries);
 int cbn_row_moments(float* rows, int64_t n_rows, int32_t n_cols, const float* target_values, int32_t normalize,
                     float* mass, float* mean, float* var, void* stream);
 
+/* ---- quantile: per query, the inverse cdf of the marginal at given
+ * probabilities -- medians, credible intervals, and (at uniform random
+ * probabilities) draws from the posterior.  No reference counterpart.  Per
+ * query row q, with r_j >= 0 the UNnormalised product row (the rows of a
+ * CBN_RUN_RAW launch) and s_j = target_values[j] the target's sample points of
+ * this call:
+ *   c_j   = the fp32 inclusive prefix sum r_0 + ... + r_j.  The association is
+ *           the kernel's own (a scan in column order, blocked by lane), a fixed
+ *           function of the row alone on a given plan.
+ *   mass  = c_{N-1}: within 2 N 2^-24 relative of the exact sum, not
+ *           necessarily the bits of cbn_plan_run_moments's mass.
+ *   per probability p: t = p * mass (one fp32 product) and
+ *   index = min{ j : r_j > 0 and c_j >= t }, or, when no column qualifies
+ *           (rounding at p = 1), max{ j : r_j > 0 }: the usual
+ *           inf{x : F(x) >= p} over the columns of positive probability.
+ *           p = 0 gives the first such column; no p gives a column of
+ *           probability 0, so uniform random p make the call a sampler.
+ *   value = s[index].
+ * index is non-decreasing in p for a given row (the minimum over a shrinking
+ * set), even where c is not monotone to the last ulp.  A row of mass 0
+ * (off-domain evidence), or of non-finite mass (a NaN or inf in a parametric
+ * row), gives index -1 and value NaN for every p; a p that is NaN or outside
+ * [0, 1] gives index -1 and value NaN for that entry only.  A row's outputs
+ * depend on that row's evidence and probabilities alone: the same bits at any
+ * position of any batch on the same plan and the same route (in-kernel or
+ * stored rows).  The two routes associate the prefix sum differently (the
+ * stored-rows kernel cannot reproduce a query kernel's lane layout), so on a
+ * plan with CBN_PLAN_QUANTILE a call with n_probs <= CBN_MAX_QUANTILES and one
+ * with more may differ by one column of positive probability on an entry whose
+ * p * mass lies within float32 rounding of a cdf step; both are within the
+ * bounds above.  All three added in ABI 5 (additive). */
+#define CBN_MAX_QUANTILES 16 /* probabilities per query served inside the query kernel */
+
+/* One launch on plans with CBN_PLAN_QUANTILE when n_probs <= CBN_MAX_QUANTILES
+ * (the query kernel scans each row in registers: no rows stored, no grid
+ * barrier, no max words).  Every other call stores the raw rows in `scratch`
+ * (device, 16-B aligned, cbn_plan_quantile_scratch floats; CBN_E_ARG when NULL) and runs
+ * cbn_row_quantile's kernel on them.  probs: device, n_probs >= 1 floats
+ * shared by every query (probs_stride 0) or row q's at probs + q *
+ * probs_stride (probs_stride >= n_probs; anything else: CBN_E_ARG).  index:
+ * device [Q, n_probs], required; value (needs target_values) and mass may be
+ * NULL.  flags: CBN_RUN_BUILD_TABLES only.  n_queries >= 1; evidence as
+ * cbn_plan_run.  Reports (and clears) a pending grid-barrier timeout of the
+ * plan as cbn_plan_run does. */
+int cbn_plan_run_quantile(cbn_plan* plan, int64_t n_queries, const float* const* evidence, int32_t n_evidence,
+                          const float* target_values /* device [N] or NULL */, const float* probs, int32_t n_probs,
+                          int64_t probs_stride, int32_t* index /* [Q, P] */, float* value /* [Q, P], NULL ok */,
+                          float* mass /* [Q], NULL ok */, float* scratch, int32_t flags, void* stream);
+
+/* Floats of scratch cbn_plan_run_quantile needs for n_queries and n_probs: 0
+ * exactly when the query kernel itself serves the call.  The scratch must be
+ * 16-B aligned (the rows are stored with 16-B accesses): CBN_E_ARG otherwise. */
+int64_t cbn_plan_quantile_scratch(const cbn_plan* plan, int64_t n_queries, int32_t n_probs);
+
+/* The same outputs from stored raw rows [n_rows, n_cols] (row-major float32,
+ * device): any n_cols >= 1 and any n_probs >= 1; 16-B loads when n_cols % 4 ==
+ * 0 and rows is 16-B aligned. */
+int cbn_row_quantile(const float* rows, int64_t n_rows, int32_t n_cols, const float* target_values,
+                     const float* probs, int32_t n_probs, int64_t probs_stride, int32_t* index, float* value,
+                     float* mass, void* stream);
+
 /* CBN_E_TIMEOUT (and clears the report) if a single-launch call of the plan
  * timed out in its grid barrier since the last report, else CBN_OK: a read of
  * the plan's host-mapped status word, no device round trip.  A caller that
@@ -347,6 +408,7 @@ int cbn_plan_check(cbn_plan* plan);
 #define CBN_PLAN_SLOTS 512     /* k_query_slots (slot-indexed evidence, global tables, >= 4 lanes per query; round 5) */
 #define CBN_PLAN_ARGMAX 1024   /* cbn_plan_run_argmax runs in the query kernel itself (no rows stored) */
 #define CBN_PLAN_MOMENTS 2048  /* cbn_plan_run_moments runs in the query kernel itself (rows stored only on request) */
+#define CBN_PLAN_QUANTILE 4096 /* cbn_plan_run_quantile runs in the query kernel itself */
 int32_t cbn_plan_flags(const cbn_plan* plan);
 
 /* Test hook: mark the plan as if a single-launch call had timed out in its
