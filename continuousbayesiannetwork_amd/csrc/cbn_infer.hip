@@ -2858,54 +2858,49 @@ int g_num_cu = 0;
 
 }  // namespace
 
-// index / value / row_max of rows [n_rows, n_cols] on `s` (k_row_argmax)
-static int launch_row_argmax(const float* rows, long long n_rows, int n_cols, const ArgmaxOut& am, hipStream_t s) {
+// The grid of a row kernel over stored rows [n_rows, n_cols] (rows_per_block =
+// kRowThreads / LR), and the kernel's VEC instance: launch(VEC tag, blocks, LR).
+// VEC (16-B pieces: n_cols % 4 == 0, aligned rows) spreads a row over LR lanes,
+// the smallest power of two with 4 LR >= n_cols, at most 64.  A non-VEC row is
+// spread the same way when `spread_scalar` (k_row_quantile), else walked by one
+// lane (LR = 1: k_row_argmax, k_row_moments).
+template <class Launch>
+static int launch_rows(const float* rows, long long n_rows, int n_cols, bool spread_scalar, Launch launch) {
     const bool vec = n_cols % 4 == 0 && reinterpret_cast<uintptr_t>(rows) % 16 == 0;
     int LR = 1;
-    if (vec)
-        while (LR < n_cols / 4 && LR < kWave) LR <<= 1;
+    if (vec || spread_scalar)
+        while (4 * LR < n_cols && LR < kWave) LR <<= 1;
     const long long rpb = kRowThreads / LR;
-    const long long blocks = std::max(1LL, std::min((n_rows + rpb - 1) / rpb, (long long)num_cu() * 16));
+    const unsigned blocks = (unsigned)std::max(1LL, std::min((n_rows + rpb - 1) / rpb, (long long)num_cu() * 16));
     if (vec)
-        hipLaunchKernelGGL(k_row_argmax<true>, dim3((unsigned)blocks), dim3(kRowThreads), 0, s, rows, n_rows, n_cols, LR, am);
+        launch(std::true_type{}, blocks, LR);
     else
-        hipLaunchKernelGGL(k_row_argmax<false>, dim3((unsigned)blocks), dim3(kRowThreads), 0, s, rows, n_rows, n_cols, LR, am);
+        launch(std::false_type{}, blocks, LR);
     HIP_TRY(hipGetLastError());
     return CBN_OK;
+}
+
+// index / value / row_max of rows [n_rows, n_cols] on `s` (k_row_argmax)
+static int launch_row_argmax(const float* rows, long long n_rows, int n_cols, const ArgmaxOut& am, hipStream_t s) {
+    return launch_rows(rows, n_rows, n_cols, false, [&](auto vec, unsigned blocks, int LR) {
+        hipLaunchKernelGGL(k_row_argmax<vec.value>, dim3(blocks), dim3(kRowThreads), 0, s, rows, n_rows, n_cols, LR, am);
+    });
 }
 
 // mass / mean / var of rows [n_rows, n_cols] on `s`, the rows divided in place when `normalize` (k_row_moments)
 static int launch_row_moments(float* rows, long long n_rows, int n_cols, bool normalize, const MomentsOut& mo,
                               hipStream_t s) {
-    const bool vec = n_cols % 4 == 0 && reinterpret_cast<uintptr_t>(rows) % 16 == 0;
-    int LR = 1;
-    if (vec)
-        while (LR < n_cols / 4 && LR < kWave) LR <<= 1;
-    const long long rpb = kRowThreads / LR;
-    const long long blocks = std::max(1LL, std::min((n_rows + rpb - 1) / rpb, (long long)num_cu() * 16));
-    if (vec)
-        hipLaunchKernelGGL(k_row_moments<true>, dim3((unsigned)blocks), dim3(kRowThreads), 0, s, rows, n_rows, n_cols, LR,
+    return launch_rows(rows, n_rows, n_cols, false, [&](auto vec, unsigned blocks, int LR) {
+        hipLaunchKernelGGL(k_row_moments<vec.value>, dim3(blocks), dim3(kRowThreads), 0, s, rows, n_rows, n_cols, LR,
                            normalize ? 1 : 0, mo);
-    else
-        hipLaunchKernelGGL(k_row_moments<false>, dim3((unsigned)blocks), dim3(kRowThreads), 0, s, rows, n_rows, n_cols, LR,
-                           normalize ? 1 : 0, mo);
-    HIP_TRY(hipGetLastError());
-    return CBN_OK;
+    });
 }
 
 // the quantiles of rows [n_rows, n_cols] on `s` (k_row_quantile)
 static int launch_row_quantile(const float* rows, long long n_rows, int n_cols, const QuantileOut& qu, hipStream_t s) {
-    const bool vec = n_cols % 4 == 0 && reinterpret_cast<uintptr_t>(rows) % 16 == 0;
-    int LR = 1;
-    while (4 * LR < n_cols && LR < kWave) LR <<= 1;
-    const long long rpb = kRowThreads / LR;
-    const long long blocks = std::max(1LL, std::min((n_rows + rpb - 1) / rpb, (long long)num_cu() * 16));
-    if (vec)
-        hipLaunchKernelGGL(k_row_quantile<true>, dim3((unsigned)blocks), dim3(kRowThreads), 0, s, rows, n_rows, n_cols, LR, qu);
-    else
-        hipLaunchKernelGGL(k_row_quantile<false>, dim3((unsigned)blocks), dim3(kRowThreads), 0, s, rows, n_rows, n_cols, LR, qu);
-    HIP_TRY(hipGetLastError());
-    return CBN_OK;
+    return launch_rows(rows, n_rows, n_cols, true, [&](auto vec, unsigned blocks, int LR) {
+        hipLaunchKernelGGL(k_row_quantile<vec.value>, dim3(blocks), dim3(kRowThreads), 0, s, rows, n_rows, n_cols, LR, qu);
+    });
 }
 
 int cbn::num_cu() {
@@ -3243,12 +3238,9 @@ void allow_lds(size_t bytes) {
     }
 }
 
-// the plan's arg-max runs in its query kernel (kModeArgmax): every fast-path table plan
-bool argmax_native(const cbn_plan* p) { return p->fast && !p->param && !p->direct; }
-// ... and so do its moments (kModeMoments): the same plans
-bool moments_native(const cbn_plan* p) { return argmax_native(p); }
-// ... and its quantiles (kModeQuantile), for up to CBN_MAX_QUANTILES probabilities per query
-bool quantile_native(const cbn_plan* p) { return argmax_native(p); }
+// the plan's per-row reductions run in its query kernel (kModeArgmax, kModeMoments, and kModeQuantile
+// for up to CBN_MAX_QUANTILES probabilities per query): every fast-path table plan
+bool reduce_native(const cbn_plan* p) { return p->fast && !p->param && !p->direct; }
 
 // Rows of a factor's table: the product of its observed parents' cards
 // (clamped, so a sum over the factors cannot overflow).
@@ -3294,6 +3286,49 @@ long long fused_capacity(const cbn_plan* p) {
     const long long blocks = std::min(num_cu(), kMaxSlots);  // one block per CU, one barrier slot each
     // k_query_slots and k_query_cols hold two rounds of products per lane across the barrier
     return blocks * (kQueryThreads / kWave) * (kWave / L) * ((p->slots || p->cols) && CBN_SLOTS_FUSED2 ? 2 : 1);
+}
+
+// One per-row reduction of a plan's marginals (cbn_plan_run_argmax / _moments /
+// _quantile; `name`, for messages): the checks they share, then the raw rows by
+// one of three routes.  `native`: the plan's query kernel reduces in its
+// epilogue (launch_mode<MODE> with `mx`, and `out` for its normalised rows).
+// Else the raw rows go to `rows` (`need` says what the caller must pass for
+// them) and `row_launch(rows)` reduces them: direct and parametric plans by
+// their own raw launch, and so a fast table plan when `fast_raw`; generic table
+// plans by the write pass dividing by 1.0f (IEEE x / 1 = x).  `misaligned`: a
+// buffer of this call that fails its 16-byte alignment, reported in its place.
+template <int MODE, class RowLaunch>
+int run_reduce(cbn_plan* plan, int64_t n_queries, const float* const* evidence, int32_t n_evidence, int32_t flags,
+               void* stream, const char* name, bool native, float* rows, const char* need, const char* misaligned,
+               bool fast_raw, const ModeOut& mx, float* out, RowLaunch row_launch) {
+    if (n_queries <= 0) return set_err(CBN_E_ARG, "%s: needs >= 1 query", name);
+    if (n_evidence < 0 || (n_evidence > 0 && !evidence)) return set_err(CBN_E_ARG, "%s: null evidence", name);
+    for (int i = 0; i < n_evidence; ++i)
+        if (!evidence[i]) return set_err(CBN_E_ARG, "null evidence column %d", i);
+    if (!native && !rows) return set_err(CBN_E_ARG, "%s: %s", name, need);
+    if (misaligned) return set_err(CBN_E_ARG, "%s: %s must be 16-B aligned", name, misaligned);
+    const bool table = !plan->param && !plan->direct;
+    if (table) {
+        if (n_evidence != plan->ns) return set_err(CBN_E_ARG, "plan expects %d evidence columns, got %d", plan->ns, n_evidence);
+        if (!plan->d_fac || !plan->d_slots || !plan->d_image || !plan->d_sync)
+            return set_err(CBN_E_ARG, "plan has no device buffers");
+    }
+    CBN_TRY(take_pending_timeout(plan));
+    if (!table || (fast_raw && plan->fast && !native)) {
+        // (the raw launch's per-block maxima go into the plan's own words, unused here)
+        CBN_TRY(cbn_plan_run(plan, n_queries, evidence, n_evidence, plan->d_sync + kMaxWordOff, rows,
+                             (flags & CBN_RUN_BUILD_TABLES) | CBN_RUN_RAW, stream));
+        return row_launch(rows);
+    }
+    if (flags & CBN_RUN_BUILD_TABLES) CBN_TRY(cbn_plan_build_tables(plan, stream));
+    if (!native) {
+        CBN_TRY(cbn_plan_query_write(plan, n_queries, evidence, n_evidence, plan->d_sync + kOneWordOff, rows, stream));
+        return row_launch(rows);
+    }
+    EvPtrs ev;
+    CBN_TRY(pack_evidence(plan, evidence, n_evidence, n_queries, ev));
+    return launch_mode<MODE>(plan, n_queries, ev, nullptr, 0, nullptr, out, reinterpret_cast<hipStream_t>(stream), nullptr,
+                             &mx);
 }
 
 }  // namespace
@@ -3998,7 +4033,7 @@ int cbn_row_argmax(const float* rows, int64_t n_rows, int32_t n_cols, const floa
 }
 
 int64_t cbn_plan_argmax_scratch(const cbn_plan* plan, int64_t n_queries) {
-    if (!plan || n_queries < 0 || argmax_native(plan)) return 0;
+    if (!plan || n_queries < 0 || reduce_native(plan)) return 0;
     return n_queries * (int64_t)plan->N;
 }
 
@@ -4007,45 +4042,14 @@ int cbn_plan_run_argmax(cbn_plan* plan, int64_t n_queries, const float* const* e
                         int32_t flags, void* stream) {
     if (!plan) return set_err(CBN_E_ARG, "null plan");
     if (!index) return set_err(CBN_E_ARG, "cbn_plan_run_argmax: null output");
-    if (n_queries <= 0) return set_err(CBN_E_ARG, "cbn_plan_run_argmax: needs >= 1 query");
-    if (n_evidence < 0 || (n_evidence > 0 && !evidence)) return set_err(CBN_E_ARG, "cbn_plan_run_argmax: null evidence");
-    for (int i = 0; i < n_evidence; ++i)
-        if (!evidence[i]) return set_err(CBN_E_ARG, "null evidence column %d", i);
-    const bool native = argmax_native(plan);
-    if (!native && !scratch)
-        return set_err(CBN_E_ARG, "cbn_plan_run_argmax: this plan needs cbn_plan_argmax_scratch floats of scratch");
-    const bool table = !plan->param && !plan->direct;
-    if (table) {
-        if (n_evidence != plan->ns) return set_err(CBN_E_ARG, "plan expects %d evidence columns, got %d", plan->ns, n_evidence);
-        if (!plan->d_fac || !plan->d_slots || !plan->d_image || !plan->d_sync)
-            return set_err(CBN_E_ARG, "plan has no device buffers");
-    }
-    CBN_TRY(take_pending_timeout(plan));
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const ArgmaxOut am = {target_values, index, value, row_max};
-    int rc;
-    if (!table) {
-        // direct / parametric plans: their raw launch (per-block maxima into the plan's own words, unused here)
-        rc = cbn_plan_run(plan, n_queries, evidence, n_evidence, plan->d_sync + kMaxWordOff, scratch,
-                          (flags & CBN_RUN_BUILD_TABLES) | CBN_RUN_RAW, stream);
-        if (rc) return rc;
-        return launch_row_argmax(scratch, (long long)n_queries, plan->N, am, s);
-    }
-    if (flags & CBN_RUN_BUILD_TABLES) {
-        rc = cbn_plan_build_tables(plan, stream);
-        if (rc) return rc;
-    }
-    if (!native) {
-        // generic table plans: the write pass dividing by 1.0f stores the raw rows (IEEE x / 1 = x)
-        rc = cbn_plan_query_write(plan, n_queries, evidence, n_evidence, plan->d_sync + kOneWordOff, scratch, stream);
-        if (rc) return rc;
-        return launch_row_argmax(scratch, (long long)n_queries, plan->N, am, s);
-    }
-    EvPtrs ev;
-    CBN_TRY(pack_evidence(plan, evidence, n_evidence, n_queries, ev));
     ModeOut mx;
-    mx.am = am;
-    return launch_mode<kModeArgmax>(plan, n_queries, ev, nullptr, 0, nullptr, nullptr, s, nullptr, &mx);
+    mx.am = {target_values, index, value, row_max};
+    return run_reduce<kModeArgmax>(plan, n_queries, evidence, n_evidence, flags, stream, "cbn_plan_run_argmax",
+                                   reduce_native(plan), scratch, "this plan needs cbn_plan_argmax_scratch floats of scratch", nullptr,
+                                   false, mx, nullptr, [&](const float* rows) {
+                                       return launch_row_argmax(rows, (long long)n_queries, plan->N, mx.am,
+                                                                reinterpret_cast<hipStream_t>(stream));
+                                   });
 }
 
 int cbn_row_moments(float* rows, int64_t n_rows, int32_t n_cols, const float* target_values, int32_t normalize,
@@ -4058,10 +4062,7 @@ int cbn_row_moments(float* rows, int64_t n_rows, int32_t n_cols, const float* ta
                               reinterpret_cast<hipStream_t>(stream));
 }
 
-int64_t cbn_plan_moments_scratch(const cbn_plan* plan, int64_t n_queries) {
-    if (!plan || n_queries < 0 || moments_native(plan)) return 0;
-    return n_queries * (int64_t)plan->N;
-}
+int64_t cbn_plan_moments_scratch(const cbn_plan* plan, int64_t n_queries) { return cbn_plan_argmax_scratch(plan, n_queries); }
 
 int cbn_plan_run_moments(cbn_plan* plan, int64_t n_queries, const float* const* evidence, int32_t n_evidence,
                          const float* target_values, float* out, float* mass, float* mean, float* var, float* scratch,
@@ -4070,42 +4071,17 @@ int cbn_plan_run_moments(cbn_plan* plan, int64_t n_queries, const float* const* 
     if (!mass) return set_err(CBN_E_ARG, "cbn_plan_run_moments: null output");
     if ((mean || var) && !target_values)
         return set_err(CBN_E_ARG, "cbn_plan_run_moments: mean / var need the target's sample points");
-    if (n_queries <= 0) return set_err(CBN_E_ARG, "cbn_plan_run_moments: needs >= 1 query");
-    if (n_evidence < 0 || (n_evidence > 0 && !evidence)) return set_err(CBN_E_ARG, "cbn_plan_run_moments: null evidence");
-    for (int i = 0; i < n_evidence; ++i)
-        if (!evidence[i]) return set_err(CBN_E_ARG, "null evidence column %d", i);
-    const bool native = moments_native(plan);
-    float* rows = out ? out : scratch;  // fallback plans: where the raw rows go (divided in place when that is `out`)
-    if (!native && !rows)
-        return set_err(CBN_E_ARG, "cbn_plan_run_moments: this plan needs `out` or cbn_plan_moments_scratch floats of scratch");
-    if (native && reinterpret_cast<uintptr_t>(out) % 16)
-        return set_err(CBN_E_ARG, "cbn_plan_run_moments: out must be 16-B aligned");
-    const bool table = !plan->param && !plan->direct;
-    if (table) {
-        if (n_evidence != plan->ns) return set_err(CBN_E_ARG, "plan expects %d evidence columns, got %d", plan->ns, n_evidence);
-        if (!plan->d_fac || !plan->d_slots || !plan->d_image || !plan->d_sync)
-            return set_err(CBN_E_ARG, "plan has no device buffers");
-    }
-    CBN_TRY(take_pending_timeout(plan));
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const MomentsOut mo = {target_values, mass, mean, var};
-    if (!table) {
-        // direct / parametric plans: their raw launch (per-block maxima into the plan's own words, unused here)
-        CBN_TRY(cbn_plan_run(plan, n_queries, evidence, n_evidence, plan->d_sync + kMaxWordOff, rows,
-                             (flags & CBN_RUN_BUILD_TABLES) | CBN_RUN_RAW, stream));
-        return launch_row_moments(rows, (long long)n_queries, plan->N, out != nullptr, mo, s);
-    }
-    if (flags & CBN_RUN_BUILD_TABLES) CBN_TRY(cbn_plan_build_tables(plan, stream));
-    if (!native) {
-        // generic table plans: the write pass dividing by 1.0f stores the raw rows (IEEE x / 1 = x)
-        CBN_TRY(cbn_plan_query_write(plan, n_queries, evidence, n_evidence, plan->d_sync + kOneWordOff, rows, stream));
-        return launch_row_moments(rows, (long long)n_queries, plan->N, out != nullptr, mo, s);
-    }
-    EvPtrs ev;
-    CBN_TRY(pack_evidence(plan, evidence, n_evidence, n_queries, ev));
+    const bool native = reduce_native(plan);
     ModeOut mx;
-    mx.mo = mo;
-    return launch_mode<kModeMoments>(plan, n_queries, ev, nullptr, 0, nullptr, out, s, nullptr, &mx);
+    mx.mo = {target_values, mass, mean, var};
+    // fallback plans: the raw rows go to `out` when that is given, and are divided in place there
+    return run_reduce<kModeMoments>(plan, n_queries, evidence, n_evidence, flags, stream, "cbn_plan_run_moments", native,
+                                    out ? out : scratch, "this plan needs `out` or cbn_plan_moments_scratch floats of scratch",
+                                    native && reinterpret_cast<uintptr_t>(out) % 16 ? "out" : nullptr, false, mx, out,
+                                    [&](float* rows) {
+                                        return launch_row_moments(rows, (long long)n_queries, plan->N, out != nullptr,
+                                                                  mx.mo, reinterpret_cast<hipStream_t>(stream));
+                                    });
 }
 
 static bool quantile_args_ok(const float* probs, int32_t n_probs, int64_t probs_stride, const int32_t* index) {
@@ -4122,7 +4098,7 @@ int cbn_row_quantile(const float* rows, int64_t n_rows, int32_t n_cols, const fl
 }
 
 int64_t cbn_plan_quantile_scratch(const cbn_plan* plan, int64_t n_queries, int32_t n_probs) {
-    if (!plan || n_queries < 0 || (quantile_native(plan) && n_probs <= CBN_MAX_QUANTILES)) return 0;
+    if (!plan || n_queries < 0 || (reduce_native(plan) && n_probs <= CBN_MAX_QUANTILES)) return 0;
     return n_queries * (int64_t)plan->N;
 }
 
@@ -4134,43 +4110,18 @@ int cbn_plan_run_quantile(cbn_plan* plan, int64_t n_queries, const float* const*
     if (n_probs < 1) return set_err(CBN_E_ARG, "cbn_plan_run_quantile: needs >= 1 probability");
     if (probs_stride != 0 && probs_stride < n_probs)
         return set_err(CBN_E_ARG, "cbn_plan_run_quantile: probs_stride must be 0 or >= n_probs");
-    if (n_queries <= 0) return set_err(CBN_E_ARG, "cbn_plan_run_quantile: needs >= 1 query");
-    if (n_evidence < 0 || (n_evidence > 0 && !evidence)) return set_err(CBN_E_ARG, "cbn_plan_run_quantile: null evidence");
-    for (int i = 0; i < n_evidence; ++i)
-        if (!evidence[i]) return set_err(CBN_E_ARG, "null evidence column %d", i);
-    const bool native = quantile_native(plan) && n_probs <= CBN_MAX_QUANTILES;
-    if (!native && !scratch)
-        return set_err(CBN_E_ARG, "cbn_plan_run_quantile: this call needs cbn_plan_quantile_scratch floats of scratch");
-    if (!native && reinterpret_cast<uintptr_t>(scratch) % 16)
-        return set_err(CBN_E_ARG, "cbn_plan_run_quantile: scratch must be 16-B aligned");
-    const bool table = !plan->param && !plan->direct;
-    if (table) {
-        if (n_evidence != plan->ns) return set_err(CBN_E_ARG, "plan expects %d evidence columns, got %d", plan->ns, n_evidence);
-        if (!plan->d_fac || !plan->d_slots || !plan->d_image || !plan->d_sync)
-            return set_err(CBN_E_ARG, "plan has no device buffers");
-    }
-    CBN_TRY(take_pending_timeout(plan));
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const QuantileOut qu = {target_values, probs, (long long)probs_stride, index, value, mass, (int)n_probs};
-    if (!table || (plan->fast && !native)) {
-        // direct / parametric plans, and a fast table plan asked for more probabilities than its kernel
-        // serves: their raw launch (per-block maxima into the plan's own words, unused here)
-        CBN_TRY(cbn_plan_run(plan, n_queries, evidence, n_evidence, plan->d_sync + kMaxWordOff, scratch,
-                             (flags & CBN_RUN_BUILD_TABLES) | CBN_RUN_RAW, stream));
-        return launch_row_quantile(scratch, (long long)n_queries, plan->N, qu, s);
-    }
-    if (flags & CBN_RUN_BUILD_TABLES) CBN_TRY(cbn_plan_build_tables(plan, stream));
-    if (!native) {
-        // generic table plans: the write pass dividing by 1.0f stores the raw rows (IEEE x / 1 = x)
-        CBN_TRY(cbn_plan_query_write(plan, n_queries, evidence, n_evidence, plan->d_sync + kOneWordOff, scratch, stream));
-        return launch_row_quantile(scratch, (long long)n_queries, plan->N, qu, s);
-    }
-    EvPtrs ev;
-    CBN_TRY(pack_evidence(plan, evidence, n_evidence, n_queries, ev));
+    // a fast plan asked for more probabilities than its kernel serves takes its raw launch, like a direct plan
+    const bool native = reduce_native(plan) && n_probs <= CBN_MAX_QUANTILES;
     ModeOut mx;
     memset(&mx, 0, sizeof(mx));
-    mx.qu = qu;
-    return launch_mode<kModeQuantile>(plan, n_queries, ev, nullptr, 0, nullptr, nullptr, s, nullptr, &mx);
+    mx.qu = {target_values, probs, (long long)probs_stride, index, value, mass, (int)n_probs};
+    return run_reduce<kModeQuantile>(plan, n_queries, evidence, n_evidence, flags, stream, "cbn_plan_run_quantile", native,
+                                     scratch, "this call needs cbn_plan_quantile_scratch floats of scratch",
+                                     !native && reinterpret_cast<uintptr_t>(scratch) % 16 ? "scratch" : nullptr, true, mx,
+                                     nullptr, [&](const float* rows) {
+                                         return launch_row_quantile(rows, (long long)n_queries, plan->N, mx.qu,
+                                                                    reinterpret_cast<hipStream_t>(stream));
+                                     });
 }
 
 int cbn_plan_status(cbn_plan* plan, int32_t* status) {
@@ -4201,8 +4152,7 @@ int32_t cbn_plan_flags(const cbn_plan* plan) {
            (plan->fused_ok ? CBN_PLAN_FUSED : 0) | (plan->param ? CBN_PLAN_PARAMETRIC : 0) |
            (plan->vpl == 2 ? CBN_PLAN_VPL2 : 0) | (plan->direct ? CBN_PLAN_DIRECT : 0) |
            (plan->cols ? CBN_PLAN_COLS : 0) | (plan->slots ? CBN_PLAN_SLOTS : 0) |
-           (argmax_native(plan) ? CBN_PLAN_ARGMAX : 0) | (moments_native(plan) ? CBN_PLAN_MOMENTS : 0) |
-           (quantile_native(plan) ? CBN_PLAN_QUANTILE : 0);
+           (reduce_native(plan) ? CBN_PLAN_ARGMAX | CBN_PLAN_MOMENTS | CBN_PLAN_QUANTILE : 0);
 }
 
 int32_t cbn_plan_max_words(const cbn_plan* plan) {

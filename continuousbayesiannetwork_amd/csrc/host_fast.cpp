@@ -130,105 +130,101 @@ py::object run(uintptr_t fn, uintptr_t plan, py::dict evidence, py::tuple slots,
     return py::cast(out);
 }
 
-// InferenceEngine.predict's hot path: run's evidence checks, then index (int32
-// [Q]), value and row_max (float32 [Q]) -- plus `scratch_per_query` floats of
-// scratch per query for plans without the arg-max epilogue
-// (cbn_plan_argmax_scratch) -- and ONE call of cbn_plan_run_argmax (passed in
-// as `fn`) on the current stream.  tv_ptr: the target's float32 sample points
-// on the device, or 0 (value is then left to the caller's gather).  Returns
-// (index, value, row_max); None when a fast check failed; an int = the C ABI's
-// error code.
+// What the hot paths of InferenceEngine.predict, posterior and quantile share (run_argmax, run_moments,
+// run_quantile): run's evidence checks -- and the batch size must be `want_n` when that is not negative -- then
+// `scratch_per_query` floats of scratch per query when above 0 (plans whose query kernel does not serve the
+// call: cbn_plan_*_scratch) and the current stream.  Each entry point adds its outputs and ONE call of its C
+// function (`fn`), and returns a tuple; None when a fast check failed; an int = the C ABI's error code.
+// tv_ptr: the target's float32 sample points on the device, or 0.
+struct Reduce {
+    Cols c;
+    int32_t ns;  // the plan's evidence slots
+    at::TensorOptions fopt, iopt;  // float32 / int32 on the device
+    at::Tensor scratch_t;  // (freed at return: stream-ordered behind the launches that use it)
+    float* scratch;
+    hipStream_t s;
+    void* plan;
+    const float* tv;
+};
+
+float* fptr(const at::Tensor& t) { return t.defined() ? static_cast<float*>(t.data_ptr()) : nullptr; }
+
+bool reduce_begin(uintptr_t plan, py::dict& evidence, py::tuple& slots, py::object& first, int64_t device_index,
+                  bool target_observed, uintptr_t tv_ptr, int64_t want_n, int64_t scratch_per_query, Reduce& r) {
+    if (!gather(evidence, slots, first, device_index, target_observed, r.c)) return false;
+    if (want_n >= 0 && want_n != r.c.n) return false;
+    const auto dev = at::Device(at::kCUDA, (c10::DeviceIndex)device_index);
+    r.fopt = at::TensorOptions().dtype(at::kFloat).device(dev);
+    r.iopt = at::TensorOptions().dtype(at::kInt).device(dev);
+    if (scratch_per_query > 0) r.scratch_t = at::empty({r.c.n * scratch_per_query}, r.fopt);
+    r.scratch = fptr(r.scratch_t);
+    r.ns = (int32_t)PyTuple_GET_SIZE(slots.ptr());
+    r.s = c10::hip::getCurrentHIPStream(device_index).stream();
+    r.plan = reinterpret_cast<void*>(plan);
+    r.tv = reinterpret_cast<const float*>(tv_ptr);
+    return true;
+}
+
+// index (int32 [Q]), value (tv[index]; with tv_ptr 0 left to the caller's gather) and row_max (float32 [Q])
 using argmax_fn = int (*)(void*, int64_t, const float* const*, int32_t, const float*, int32_t*, float*, float*, float*,
                           int32_t, hipStream_t);
 
 py::object run_argmax(uintptr_t fn, uintptr_t plan, py::dict evidence, py::tuple slots, py::object first,
                       int64_t device_index, bool target_observed, uintptr_t tv_ptr, int64_t scratch_per_query,
                       int32_t flags) {
-    Cols c;
-    if (!gather(evidence, slots, first, device_index, target_observed, c)) return py::none();
-    const auto dev = at::Device(at::kCUDA, (c10::DeviceIndex)device_index);
-    const auto fopt = at::TensorOptions().dtype(at::kFloat).device(dev);
-    at::Tensor index = at::empty({c.n}, at::TensorOptions().dtype(at::kInt).device(dev));
-    at::Tensor value = at::empty({c.n}, fopt);
-    at::Tensor row_max = at::empty({c.n}, fopt);
-    at::Tensor scratch;  // (freed at return: stream-ordered behind the launches that use it)
-    if (scratch_per_query > 0) scratch = at::empty({c.n * scratch_per_query}, fopt);
-    const hipStream_t s = c10::hip::getCurrentHIPStream(device_index).stream();
-    const int rc = reinterpret_cast<argmax_fn>(fn)(
-        reinterpret_cast<void*>(plan), c.n, c.p, (int32_t)PyTuple_GET_SIZE(slots.ptr()),
-        reinterpret_cast<const float*>(tv_ptr), static_cast<int32_t*>(index.data_ptr()),
-        static_cast<float*>(value.data_ptr()), static_cast<float*>(row_max.data_ptr()),
-        scratch.defined() ? static_cast<float*>(scratch.data_ptr()) : nullptr, flags, s);
+    Reduce r;
+    if (!reduce_begin(plan, evidence, slots, first, device_index, target_observed, tv_ptr, -1, scratch_per_query, r))
+        return py::none();
+    at::Tensor index = at::empty({r.c.n}, r.iopt);
+    at::Tensor value = at::empty({r.c.n}, r.fopt), row_max = at::empty({r.c.n}, r.fopt);
+    const int rc = reinterpret_cast<argmax_fn>(fn)(r.plan, r.c.n, r.c.p, r.ns, r.tv, index.data_ptr<int32_t>(),
+                                                   fptr(value), fptr(row_max), r.scratch, flags, r.s);
     if (rc) return py::int_(rc);
     return py::make_tuple(index, value, row_max);
 }
 
-// InferenceEngine.posterior's hot path, run_argmax's sibling: run's evidence
-// checks, then mass, mean and var (float32 [Q]; tv_ptr: the target's float32
-// sample points on the device), the [Q, n_samples] pdf when `rows` -- else `scratch_per_query` floats of scratch per
-// query for plans without the moments epilogue (cbn_plan_moments_scratch) --
-// and ONE call of cbn_plan_run_moments (passed in as `fn`) on the current
-// stream.  Returns (pdf or None, mass, mean, var); None when a fast check
-// failed; an int = the C ABI's error code.
+// (pdf or None, mass, mean, var): float32 [Q], and the [Q, n_samples] pdf when `rows` (no scratch then)
 using moments_fn = int (*)(void*, int64_t, const float* const*, int32_t, const float*, float*, float*, float*, float*,
                            float*, int32_t, hipStream_t);
 
 py::object run_moments(uintptr_t fn, uintptr_t plan, py::dict evidence, py::tuple slots, py::object first,
                        int64_t device_index, int64_t n_samples, bool target_observed, uintptr_t tv_ptr, bool rows,
                        int64_t scratch_per_query, int32_t flags) {
-    Cols c;
-    if (!gather(evidence, slots, first, device_index, target_observed, c)) return py::none();
-    const auto fopt = at::TensorOptions().dtype(at::kFloat).device(at::Device(at::kCUDA, (c10::DeviceIndex)device_index));
-    at::Tensor mass = at::empty({c.n}, fopt), mean = at::empty({c.n}, fopt), var = at::empty({c.n}, fopt);
-    at::Tensor pdf, scratch;  // (scratch freed at return: stream-ordered behind the launches that use it)
-    if (rows) pdf = at::empty({c.n, n_samples}, fopt);
-    else if (scratch_per_query > 0) scratch = at::empty({c.n * scratch_per_query}, fopt);
-    auto p = [](const at::Tensor& t) { return t.defined() ? static_cast<float*>(t.data_ptr()) : nullptr; };
-    const hipStream_t s = c10::hip::getCurrentHIPStream(device_index).stream();
-    const int rc = reinterpret_cast<moments_fn>(fn)(reinterpret_cast<void*>(plan), c.n, c.p,
-                                                    (int32_t)PyTuple_GET_SIZE(slots.ptr()),
-                                                    reinterpret_cast<const float*>(tv_ptr), p(pdf), p(mass), p(mean),
-                                                    p(var), p(scratch), flags, s);
+    Reduce r;
+    if (!reduce_begin(plan, evidence, slots, first, device_index, target_observed, tv_ptr, -1,
+                      rows ? 0 : scratch_per_query, r))
+        return py::none();
+    at::Tensor mass = at::empty({r.c.n}, r.fopt), mean = at::empty({r.c.n}, r.fopt), var = at::empty({r.c.n}, r.fopt);
+    at::Tensor pdf;
+    if (rows) pdf = at::empty({r.c.n, n_samples}, r.fopt);
+    const int rc = reinterpret_cast<moments_fn>(fn)(r.plan, r.c.n, r.c.p, r.ns, r.tv, fptr(pdf), fptr(mass), fptr(mean),
+                                                    fptr(var), r.scratch, flags, r.s);
     if (rc) return py::int_(rc);
-    return py::make_tuple(pdf.defined() ? py::cast(pdf) : py::object(py::none()), mass, mean, var);
+    return py::make_tuple(rows ? py::cast(pdf) : py::object(py::none()), mass, mean, var);
 }
 
-// InferenceEngine.quantile's hot path, run_moments's sibling: run's evidence
-// checks, then index (int32 [Q, P]), value (float32 [Q, P]) and mass (float32
-// [Q]) -- plus `scratch_per_query` floats of scratch per query when the query
-// kernel does not serve the call (cbn_plan_quantile_scratch) -- and ONE call of
-// cbn_plan_run_quantile (passed in as `fn`) on the current stream.  probs: a
-// contiguous float32 tensor on the device, [P] for every query or [Q, P].
-// Returns (index, value, mass); None when a fast check failed; an int = the C
-// ABI's error code.
+// (index int32 [Q, P], value float32 [Q, P], mass float32 [Q]).  probs: contiguous float32 on the device, [P] or [Q, P]
 using quantile_fn = int (*)(void*, int64_t, const float* const*, int32_t, const float*, const float*, int32_t, int64_t,
                             int32_t*, float*, float*, float*, int32_t, hipStream_t);
 
 py::object run_quantile(uintptr_t fn, uintptr_t plan, py::dict evidence, py::tuple slots, py::object first,
                         int64_t device_index, bool target_observed, uintptr_t tv_ptr, py::object probs_obj,
                         int64_t scratch_per_query, int32_t flags) {
-    Cols c;
-    if (!gather(evidence, slots, first, device_index, target_observed, c)) return py::none();
     if (!THPVariable_Check(probs_obj.ptr())) return py::none();
     const at::Tensor& pt = THPVariable_Unpack(probs_obj.ptr());
     if (pt.scalar_type() != at::kFloat || !pt.is_cuda() || pt.get_device() != device_index || !pt.is_contiguous() ||
-        pt.dim() < 1 || pt.dim() > 2 || pt.size(-1) < 1 || (pt.dim() == 2 && pt.size(0) != c.n))
+        pt.dim() < 1 || pt.dim() > 2 || pt.size(-1) < 1)
+        return py::none();
+    Reduce r;
+    if (!reduce_begin(plan, evidence, slots, first, device_index, target_observed, tv_ptr,
+                      pt.dim() == 2 ? pt.size(0) : -1, scratch_per_query, r))
         return py::none();
     const int64_t P = pt.size(-1);
-    const auto dev = at::Device(at::kCUDA, (c10::DeviceIndex)device_index);
-    const auto fopt = at::TensorOptions().dtype(at::kFloat).device(dev);
-    at::Tensor index = at::empty({c.n, P}, at::TensorOptions().dtype(at::kInt).device(dev));
-    at::Tensor value = at::empty({c.n, P}, fopt);
-    at::Tensor mass = at::empty({c.n}, fopt);
-    at::Tensor scratch;  // (freed at return: stream-ordered behind the launches that use it)
-    if (scratch_per_query > 0) scratch = at::empty({c.n * scratch_per_query}, fopt);
-    const hipStream_t s = c10::hip::getCurrentHIPStream(device_index).stream();
-    const int rc = reinterpret_cast<quantile_fn>(fn)(
-        reinterpret_cast<void*>(plan), c.n, c.p, (int32_t)PyTuple_GET_SIZE(slots.ptr()),
-        reinterpret_cast<const float*>(tv_ptr), static_cast<const float*>(pt.data_ptr()), (int32_t)P,
-        pt.dim() == 2 ? P : 0, static_cast<int32_t*>(index.data_ptr()), static_cast<float*>(value.data_ptr()),
-        static_cast<float*>(mass.data_ptr()), scratch.defined() ? static_cast<float*>(scratch.data_ptr()) : nullptr,
-        flags, s);
+    at::Tensor index = at::empty({r.c.n, P}, r.iopt);
+    at::Tensor value = at::empty({r.c.n, P}, r.fopt), mass = at::empty({r.c.n}, r.fopt);
+    const int rc = reinterpret_cast<quantile_fn>(fn)(r.plan, r.c.n, r.c.p, r.ns, r.tv, fptr(pt), (int32_t)P,
+                                                     pt.dim() == 2 ? P : 0, index.data_ptr<int32_t>(), fptr(value),
+                                                     fptr(mass), r.scratch, flags, r.s);
     if (rc) return py::int_(rc);
     return py::make_tuple(index, value, mass);
 }

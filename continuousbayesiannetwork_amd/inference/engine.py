@@ -211,11 +211,149 @@ def domain_index_host(values: torch.Tensor, domain: torch.Tensor) -> torch.Tenso
     return torch.where(domain[i] == values, i, torch.full_like(i, -1)).to(torch.int32)
 
 
+@dataclass(frozen=True, eq=False)
+class _Reduction:
+    """One per-query reduction of the target's marginal (predict, posterior,
+    quantile), stated as what differs between them; ``InferenceEngine._reduce``
+    is everything they share.  ``arg`` is the operation's own argument
+    (predict: None, posterior: ``rows``, quantile: the probabilities)."""
+
+    c_name: str  # the C function (include/cbn_amd.h); the general path calls it, the hot path passes its address
+    host_name: str  # the native hot path's entry point (csrc/host_fast.cpp)
+    points: object  # (plan, device) -> the target's sample points as the kernels read them (float32 tensor), or None
+    # (host entry point, C function address, plan, fp) -> the hot path's call, bound once per _FastPath to the
+    # plan's constants and its scratch floats per query: (evidence, points' address or 0, arg, flags) -> host's result
+    bind: object
+    # (lib, handle of the plan run, plan, n_queries, device, arg) -> (outputs, their C arguments, scratch floats)
+    general: object
+    prepare: object = None  # (arg, device) -> arg as `bind`'s call and `general` take it; raises on a bad one
+    check: object = None  # (arg, n_queries): raises before anything of the general path is marked or launched
+    finish: object = None  # (plan, device, outputs, points) -> what the call returns (None: the outputs)
+
+
+def _f32(device, *shape) -> torch.Tensor:
+    return torch.empty(shape, dtype=torch.float32, device=device)
+
+
+def _readable_points(plan: "Plan", device):
+    """The plan's own target sample points when the kernels can read them
+    (contiguous float32 on the plan's device), else None: predict then gathers
+    ``value`` in torch, in the domain's own dtype."""
+    t = plan.target_domain
+    ok = t.dtype is torch.float32 and t.device == device and t.is_contiguous() and t.numel() == plan.n_samples
+    return t if ok else None
+
+
+def _float_points(plan: "Plan", device) -> torch.Tensor:
+    """The plan's target sample points as the kernels read them: the plan's own
+    tensor when it is contiguous float32 on the device, else one such copy for
+    the call (kept alive past the launch: stream-ordered free)."""
+    t = plan.target_domain
+    if t.dtype is torch.float32 and t.device == device and t.is_contiguous():
+        return t
+    return t.to(device=device, dtype=torch.float32).contiguous()
+
+
+def _bound(plan, fp):
+    """What every hot-path call passes unchanged for as long as ``fp`` lives."""
+    return plan.handle.value, fp.slot_keys, fp.first, fp.device.index, plan.target_observed
+
+
+def _argmax_bind(host, fn, plan, fp):
+    handle, keys, first, dev, tobs = _bound(plan, fp)
+    per_q = int(fp.lib.cbn_plan_argmax_scratch(plan.handle, 1))
+    return lambda evidence, tv, arg, flags: host(fn, handle, evidence, keys, first, dev, tobs, tv, per_q, flags)
+
+
+def _argmax_general(lib, handle, plan, n, device, arg):
+    res = (torch.empty(n, dtype=torch.int32, device=device), _f32(device, n), _f32(device, n))
+    return res, [_native.ptr(t) for t in res], int(lib.cbn_plan_argmax_scratch(handle, n))
+
+
+def _argmax_finish(plan, device, res, tv):
+    if tv is not None:
+        return res
+    index, _, row_max = res
+    return index, plan.target_domain.to(device)[index.long()], row_max
+
+
+_ARGMAX = _Reduction(
+    "cbn_plan_run_argmax", "run_argmax", _readable_points, _argmax_bind, _argmax_general, finish=_argmax_finish)
+
+
+def _moments_bind(host, fn, plan, fp):
+    handle, keys, first, dev, tobs = _bound(plan, fp)
+    N, per_q = plan.n_samples, int(fp.lib.cbn_plan_moments_scratch(plan.handle, 1))
+    return lambda evidence, tv, rows, flags: host(fn, handle, evidence, keys, first, dev, N, tobs, tv, rows, per_q, flags)
+
+
+def _moments_general(lib, handle, plan, n, device, rows):
+    pdf = _f32(device, n, plan.n_samples) if rows else None
+    mass, mean, var = _f32(device, n), _f32(device, n), _f32(device, n)
+    args = [_native.ptr(pdf) if rows else None, _native.ptr(mass), _native.ptr(mean), _native.ptr(var)]
+    return (pdf, mass, mean, var), args, 0 if rows else int(lib.cbn_plan_moments_scratch(handle, n))
+
+
+def _moments_finish(plan, device, res, tv):
+    tq = res[1].shape[0] if plan.target_observed else 1
+    return (*res, plan.target_domain.unsqueeze(0).expand(tq, -1))
+
+
+_MOMENTS = _Reduction(
+    "cbn_plan_run_moments", "run_moments", _float_points, _moments_bind, _moments_general, finish=_moments_finish)
+
+
+def _probs(probs, device) -> torch.Tensor:
+    """``quantile``'s probabilities as the kernels read them: a contiguous
+    float32 tensor [P] or [Q, P] on the device.  A host sequence or CPU
+    tensor is range-checked here (ValueError for NaN or a value outside
+    [0, 1]); a device tensor is not (no sync: the kernel's -1 / NaN rule
+    applies to a bad entry)."""
+    if not isinstance(probs, torch.Tensor):
+        probs = torch.as_tensor(probs, dtype=torch.float32)
+    if probs.dim() == 0:
+        probs = probs.reshape(1)
+    if probs.dim() > 2 or probs.shape[-1] < 1:
+        raise ValueError(f"probs must be [P] or [n_queries, P] with P >= 1, got shape {tuple(probs.shape)}")
+    if not probs.is_floating_point():
+        probs = probs.to(torch.float32)
+    if probs.device.type == "cpu" and not bool(((probs >= 0) & (probs <= 1)).all()):
+        raise ValueError("probs must lie in [0, 1]")
+    if probs.device != device or probs.dtype is not torch.float32 or not probs.is_contiguous():
+        probs = probs.to(device=device, dtype=torch.float32).contiguous()
+    return probs
+
+
+def _probs_rows(probs, n_queries):
+    if probs.dim() == 2 and probs.shape[0] != n_queries:
+        raise ValueError(f"probs has {probs.shape[0]} rows for {n_queries} queries")
+
+
+def _quantile_bind(host, fn, plan, fp):
+    handle, keys, first, dev, tobs = _bound(plan, fp)
+    few = _native.CBN_MAX_QUANTILES  # scratch floats per query at P <= / > few
+    per_q = [int(fp.lib.cbn_plan_quantile_scratch(plan.handle, 1, P)) for P in (few, few + 1)]
+    return lambda evidence, tv, probs, flags: host(fn, handle, evidence, keys, first, dev, tobs, tv, probs,
+                                                   per_q[probs.shape[-1] > few], flags)
+
+
+def _quantile_general(lib, handle, plan, n, device, probs):
+    P = probs.shape[-1]
+    res = (torch.empty((n, P), dtype=torch.int32, device=device), _f32(device, n, P), _f32(device, n))
+    args = [_native.ptr(probs), P, P if probs.dim() == 2 else 0, *[_native.ptr(t) for t in res]]
+    return res, args, int(lib.cbn_plan_quantile_scratch(handle, n, P))
+
+
+_QUANTILE = _Reduction(
+    "cbn_plan_run_quantile", "run_quantile", _float_points, _quantile_bind, _quantile_general,
+    prepare=_probs, check=_probs_rows)
+
+
 class _FastPath:
     """Everything the hot path needs for one cached (target, evidence keys, N)."""
 
     __slots__ = ("plan", "device", "first", "ptrs", "max_ptr", "lib", "tdom", "host", "run_fn", "slot_keys",
-                 "scale_fn", "host_scale", "words", "redraw", "runner", "argmax", "moments", "quantile")
+                 "scale_fn", "host_scale", "words", "redraw", "runner", "reduce")
 
     def __init__(self, plan: "Plan", device: torch.device, first_key):
         self.plan = plan
@@ -235,10 +373,8 @@ class _FastPath:
         nw = self.lib.cbn_plan_max_words(plan.handle)
         self.words = torch.zeros(nw, dtype=torch.int32, device=device) if nw > 0 else None
         self.runner = None  # native Runner of this fast path (InferenceEngine._runner), built on first use
-        self.argmax = None  # predict: (host_fast.run_argmax, cbn_plan_run_argmax, scratch floats per query)
-        self.moments = None  # posterior: (host_fast.run_moments, cbn_plan_run_moments, scratch floats per query)
-        # quantile: (host_fast.run_quantile, cbn_plan_run_quantile, scratch floats per query at P <= / > CBN_MAX_QUANTILES)
-        self.quantile = None
+        # per _Reduction used on this path: its hot-path call (_Reduction.bind)
+        self.reduce = {}
 
 
 class InferenceEngine:
@@ -885,6 +1021,14 @@ class InferenceEngine:
         fp = self._fast.get((target, tuple(evidence_keys), N_max))
         return 0 if fp is None or fp.words is None else int(fp.words.numel())
 
+    def _build_flag(self, plan: Plan) -> int:
+        """``_flags(plan) & CBN_RUN_BUILD_TABLES`` with the same bookkeeping, for
+        the calls that take no other flag (no ``timed`` / ``fused`` lookups)."""
+        if self.cache_tables and plan.tables_built:
+            return 0
+        plan.tables_built = self.cache_tables
+        return _native.CBN_RUN_BUILD_TABLES
+
     def _flags(self, plan: Plan) -> int:
         f = 0
         if not (self.cache_tables and plan.tables_built):
@@ -996,52 +1140,54 @@ class InferenceEngine:
 
         Takes and rejects exactly the calls ``infer`` does (same plan cache,
         redraw handling, [Q, N] column routing, conversions and errors)."""
+        return self._reduce(_ARGMAX, target, evidence, N_max)
+
+    def _reduce(self, op: _Reduction, target: str, evidence: Dict[str, torch.Tensor], N_max: int, arg=None):
+        """One per-query reduction (``op``: predict, posterior, quantile) of a
+        call ``infer`` would take: its plan and draws (``call_plan``), the hot
+        path (op.host_name in csrc/host_fast.cpp: the native evidence checks,
+        the outputs, one library call) and, when those checks decline the
+        evidence, the general path (``_general_call``: conversions, [Q, N]
+        columns, the reference's errors -- raised before anything is
+        launched).  A plan rebuilt per call is destroyed, raise or not."""
         plan, fp = self.call_plan(target, evidence, N_max)  # evidence=None raises AttributeError, as infer
         device = fp.device if fp is not None else _native.require_gpu(self.bn.device)
         try:
+            if op.prepare is not None:
+                arg = op.prepare(arg, device)
+            tv = op.points(plan, device)
+            res = None
             if fp is not None:
-                res = self._predict_fast(fp, evidence)
-                if res is not None:
-                    return res
-            n_queries = next(iter(evidence.values())).shape[0] if len(evidence) > 0 else 1
-            return self._predict(plan, dict(evidence.items()), n_queries, device)
+                call = fp.reduce.get(op)
+                if call is None:
+                    call = fp.reduce[op] = op.bind(getattr(_native.load_host(), op.host_name),
+                                                   ctypes.cast(getattr(fp.lib, op.c_name), ctypes.c_void_p).value, plan, fp)
+                built = plan.tables_built
+                res = call(evidence, tv.data_ptr() if tv is not None else 0, arg, self._build_flag(plan))
+                if res is None:  # nothing launched: the tables are still to be built by the launch that runs
+                    plan.tables_built = built
+                elif type(res) is int:
+                    _native.check(res, op.c_name)
+            if res is None:
+                lib = _native.load()
+                n_queries = next(iter(evidence.values())).shape[0] if len(evidence) > 0 else 1
+                if op.check is not None:
+                    op.check(arg, n_queries)
+                run_plan, cols, flags = self._general_call(plan, dict(evidence.items()), n_queries, device)
+                res, args, ns = op.general(lib, run_plan.handle, plan, n_queries, device, arg)
+                scratch = _f32(device, ns) if ns > 0 else None
+                ptrs = (ctypes.c_void_p * max(1, len(cols)))(*[c.data_ptr() for c in cols])
+                with torch.cuda.device(device):
+                    rc = getattr(lib, op.c_name)(run_plan.handle, n_queries, ptrs, len(cols),
+                                                 _native.ptr(tv) if tv is not None else None, *args,
+                                                 _native.ptr(scratch) if scratch is not None else None, flags,
+                                                 _native.stream_ptr(device))
+                    _native.check(rc, op.c_name)
+            return res if op.finish is None else op.finish(plan, device, res, tv)
         finally:
             if fp is None:  # a plan rebuilt per call
                 torch.cuda.current_stream(device).synchronize()
                 plan.destroy()
-
-    @staticmethod
-    def _target_values(plan: Plan, device) -> int:
-        """Device address of the plan's target sample points when the kernels
-        can read them (contiguous float32 on the plan's device), else 0 (the
-        caller gathers in torch)."""
-        t = plan.target_domain
-        ok = t.dtype is torch.float32 and t.device == device and t.is_contiguous() and t.numel() == plan.n_samples
-        return t.data_ptr() if ok else 0
-
-    def _predict_fast(self, fp: "_FastPath", evidence):
-        """predict's hot path (host_fast.run_argmax: the native evidence checks,
-        the outputs, one library call); None when those checks reject the
-        evidence (conversions / the reference's errors: ``_predict``)."""
-        plan = fp.plan
-        if fp.argmax is None:
-            fn = ctypes.cast(fp.lib.cbn_plan_run_argmax, ctypes.c_void_p).value
-            fp.argmax = (_native.load_host().run_argmax, fn, int(fp.lib.cbn_plan_argmax_scratch(plan.handle, 1)))
-        host, fn, per_q = fp.argmax
-        tv = self._target_values(plan, fp.device)
-        built = plan.tables_built
-        flags = self._flags(plan) & _native.CBN_RUN_BUILD_TABLES
-        res = host(fn, plan.handle.value, evidence, fp.slot_keys, fp.first, fp.device.index, plan.target_observed,
-                   tv, per_q, flags)
-        if res is None:  # nothing launched
-            plan.tables_built = built
-            return None
-        if type(res) is int:
-            _native.check(res, "cbn_plan_run_argmax")
-        index, value, row_max = res
-        if not tv:
-            value = plan.target_domain.to(fp.device)[index.long()]
-        return index, value, row_max
 
     def _general_call(self, plan: Plan, evidence, n_queries: int, device):
         """What the general path of a per-query reduction (predict, posterior)
@@ -1072,28 +1218,8 @@ class InferenceEngine:
                 flags = _native.CBN_RUN_BUILD_TABLES
                 run_plan.tables_built = True
         else:
-            flags = self._flags(plan) & _native.CBN_RUN_BUILD_TABLES
+            flags = self._build_flag(plan)
         return run_plan, cols, flags
-
-    def _predict(self, plan: Plan, evidence, n_queries: int, device):
-        """predict's general path (``_general_call``)."""
-        lib = _native.load()
-        run_plan, cols, flags = self._general_call(plan, evidence, n_queries, device)
-        index = torch.empty(n_queries, dtype=torch.int32, device=device)
-        value = torch.empty(n_queries, dtype=torch.float32, device=device)
-        row_max = torch.empty(n_queries, dtype=torch.float32, device=device)
-        ns = int(lib.cbn_plan_argmax_scratch(run_plan.handle, n_queries))
-        scratch = torch.empty(ns, dtype=torch.float32, device=device) if ns > 0 else None
-        tv = self._target_values(plan, device)
-        ptrs = (ctypes.c_void_p * max(1, len(cols)))(*[c.data_ptr() for c in cols])
-        with torch.cuda.device(device):
-            _native.check(lib.cbn_plan_run_argmax(run_plan.handle, n_queries, ptrs, len(cols), tv or None,
-                                                  _native.ptr(index), _native.ptr(value), _native.ptr(row_max),
-                                                  _native.ptr(scratch) if scratch is not None else None, flags,
-                                                  _native.stream_ptr(device)), "cbn_plan_run_argmax")
-        if not tv:
-            value = plan.target_domain.to(device)[index.long()]
-        return index, value, row_max
 
     def predict_flags(self, target: str, evidence_keys, N_max: int) -> int:
         """cbn_plan_flags of the cached (target, evidence keys, N) plan (0: none
@@ -1128,91 +1254,9 @@ class InferenceEngine:
     def posterior_domain(self, target: str, evidence: Dict[str, torch.Tensor], N_max: int, rows: bool = True):
         """``posterior`` plus the target domain of this call in ``infer``'s
         shape ([n_queries or 1, N_max]): (pdf or None, mass, mean, var, domain)."""
-        plan, fp = self.call_plan(target, evidence, N_max)  # evidence=None raises AttributeError, as infer
-        device = fp.device if fp is not None else _native.require_gpu(self.bn.device)
-        try:
-            res = self._posterior_fast(fp, evidence, rows) if fp is not None else None
-            if res is None:
-                n_queries = next(iter(evidence.values())).shape[0] if len(evidence) > 0 else 1
-                res = self._posterior(plan, dict(evidence.items()), n_queries, device, rows)
-            tq = res[1].shape[0] if plan.target_observed else 1
-            return (*res, plan.target_domain.unsqueeze(0).expand(tq, -1))
-        finally:
-            if fp is None:  # a plan rebuilt per call
-                torch.cuda.current_stream(device).synchronize()
-                plan.destroy()
-
-    @staticmethod
-    def _target_points(plan: Plan, device) -> torch.Tensor:
-        """The plan's target sample points as the kernels read them: the
-        plan's own tensor when it is contiguous float32 on the device, else one
-        such copy for the call."""
-        t = plan.target_domain
-        if t.dtype is torch.float32 and t.device == device and t.is_contiguous():
-            return t
-        return t.to(device=device, dtype=torch.float32).contiguous()
-
-    def _posterior_fast(self, fp: "_FastPath", evidence, rows: bool):
-        """posterior's hot path (host_fast.run_moments: the native evidence
-        checks, the outputs, one library call); None when those checks reject
-        the evidence (conversions / the reference's errors: ``_posterior``)."""
-        plan = fp.plan
-        if fp.moments is None:
-            fn = ctypes.cast(fp.lib.cbn_plan_run_moments, ctypes.c_void_p).value
-            fp.moments = (_native.load_host().run_moments, fn, int(fp.lib.cbn_plan_moments_scratch(plan.handle, 1)))
-        host, fn, per_q = fp.moments
-        tv = self._target_points(plan, fp.device)  # (kept alive past the launch: stream-ordered free)
-        built = plan.tables_built
-        flags = self._flags(plan) & _native.CBN_RUN_BUILD_TABLES
-        res = host(fn, plan.handle.value, evidence, fp.slot_keys, fp.first, fp.device.index, plan.n_samples,
-                   plan.target_observed, tv.data_ptr(), rows, per_q, flags)
-        if res is None:  # nothing launched
-            plan.tables_built = built
-            return None
-        if type(res) is int:
-            _native.check(res, "cbn_plan_run_moments")
-        return res
-
-    def _posterior(self, plan: Plan, evidence, n_queries: int, device, rows: bool):
-        """posterior's general path (``_general_call``)."""
-        lib = _native.load()
-        run_plan, cols, flags = self._general_call(plan, evidence, n_queries, device)
-        pdf = torch.empty((n_queries, plan.n_samples), dtype=torch.float32, device=device) if rows else None
-        mass, mean, var = (torch.empty(n_queries, dtype=torch.float32, device=device) for _ in range(3))
-        ns = 0 if rows else int(lib.cbn_plan_moments_scratch(run_plan.handle, n_queries))
-        scratch = torch.empty(ns, dtype=torch.float32, device=device) if ns > 0 else None
-        tv = self._target_points(plan, device)
-        ptrs = (ctypes.c_void_p * max(1, len(cols)))(*[c.data_ptr() for c in cols])
-        with torch.cuda.device(device):
-            _native.check(lib.cbn_plan_run_moments(run_plan.handle, n_queries, ptrs, len(cols), _native.ptr(tv),
-                                                   _native.ptr(pdf) if rows else None, _native.ptr(mass),
-                                                   _native.ptr(mean), _native.ptr(var),
-                                                   _native.ptr(scratch) if scratch is not None else None, flags,
-                                                   _native.stream_ptr(device)), "cbn_plan_run_moments")
-        return pdf, mass, mean, var
+        return self._reduce(_MOMENTS, target, evidence, N_max, rows)
 
     # ------------------------------------------------------------ quantile --
-    @staticmethod
-    def _probs(probs, device) -> torch.Tensor:
-        """``quantile``'s probabilities as the kernels read them: a contiguous
-        float32 tensor [P] or [Q, P] on the device.  A host sequence or CPU
-        tensor is range-checked here (ValueError for NaN or a value outside
-        [0, 1]); a device tensor is not (no sync: the kernel's -1 / NaN rule
-        applies to a bad entry)."""
-        if not isinstance(probs, torch.Tensor):
-            probs = torch.as_tensor(probs, dtype=torch.float32)
-        if probs.dim() == 0:
-            probs = probs.reshape(1)
-        if probs.dim() > 2 or probs.shape[-1] < 1:
-            raise ValueError(f"probs must be [P] or [n_queries, P] with P >= 1, got shape {tuple(probs.shape)}")
-        if not probs.is_floating_point():
-            probs = probs.to(torch.float32)
-        if probs.device.type == "cpu" and not bool(((probs >= 0) & (probs <= 1)).all()):
-            raise ValueError("probs must lie in [0, 1]")
-        if probs.device != device or probs.dtype is not torch.float32 or not probs.is_contiguous():
-            probs = probs.to(device=device, dtype=torch.float32).contiguous()
-        return probs
-
     def quantile(self, target: str, evidence: Dict[str, torch.Tensor], N_max: int, probs):
         """Per query and probability, the inverse cdf of the target's marginal:
         ``(index int32 [n_queries, P], value float32 [n_queries, P], mass
@@ -1239,65 +1283,9 @@ class InferenceEngine:
 
         Takes and rejects exactly the calls ``infer`` does (same plan cache,
         redraw handling, [Q, N] column routing, conversions and errors)."""
-        plan, fp = self.call_plan(target, evidence, N_max)  # evidence=None raises AttributeError, as infer
-        device = fp.device if fp is not None else _native.require_gpu(self.bn.device)
-        try:
-            pt = self._probs(probs, device)
-            res = self._quantile_fast(fp, evidence, pt) if fp is not None else None
-            if res is None:
-                n_queries = next(iter(evidence.values())).shape[0] if len(evidence) > 0 else 1
-                res = self._quantile(plan, dict(evidence.items()), n_queries, device, pt)
-            return res
-        finally:
-            if fp is None:  # a plan rebuilt per call
-                torch.cuda.current_stream(device).synchronize()
-                plan.destroy()
+        return self._reduce(_QUANTILE, target, evidence, N_max, probs)
 
-    def _quantile_fast(self, fp: "_FastPath", evidence, probs: torch.Tensor):
-        """quantile's hot path (host_fast.run_quantile: the native evidence
-        checks, the outputs, one library call); None when those checks reject
-        the evidence (conversions / the reference's errors: ``_quantile``)."""
-        plan = fp.plan
-        if fp.quantile is None:
-            fn = ctypes.cast(fp.lib.cbn_plan_run_quantile, ctypes.c_void_p).value
-            fp.quantile = (_native.load_host().run_quantile, fn,
-                           int(fp.lib.cbn_plan_quantile_scratch(plan.handle, 1, 1)),
-                           int(fp.lib.cbn_plan_quantile_scratch(plan.handle, 1, _native.CBN_MAX_QUANTILES + 1)))
-        host, fn, per_q, per_q_many = fp.quantile
-        tv = self._target_points(plan, fp.device)  # (kept alive past the launch: stream-ordered free)
-        built = plan.tables_built
-        flags = self._flags(plan) & _native.CBN_RUN_BUILD_TABLES
-        res = host(fn, plan.handle.value, evidence, fp.slot_keys, fp.first, fp.device.index, plan.target_observed,
-                   tv.data_ptr(), probs, per_q if probs.shape[-1] <= _native.CBN_MAX_QUANTILES else per_q_many, flags)
-        if res is None:  # nothing launched
-            plan.tables_built = built
-            return None
-        if type(res) is int:
-            _native.check(res, "cbn_plan_run_quantile")
-        return res
-
-    def _quantile(self, plan: Plan, evidence, n_queries: int, device, probs: torch.Tensor):
-        """quantile's general path (``_general_call``)."""
-        lib = _native.load()
-        # (before _general_call, which marks the plan's tables as built: nothing is launched on this raise)
-        if probs.dim() == 2 and probs.shape[0] != n_queries:
-            raise ValueError(f"probs has {probs.shape[0]} rows for {n_queries} queries")
-        run_plan, cols, flags = self._general_call(plan, evidence, n_queries, device)
-        P = probs.shape[-1]
-        index = torch.empty((n_queries, P), dtype=torch.int32, device=device)
-        value = torch.empty((n_queries, P), dtype=torch.float32, device=device)
-        mass = torch.empty(n_queries, dtype=torch.float32, device=device)
-        ns = int(lib.cbn_plan_quantile_scratch(run_plan.handle, n_queries, P))
-        scratch = torch.empty(ns, dtype=torch.float32, device=device) if ns > 0 else None
-        tv = self._target_points(plan, device)
-        ptrs = (ctypes.c_void_p * max(1, len(cols)))(*[c.data_ptr() for c in cols])
-        with torch.cuda.device(device):
-            _native.check(lib.cbn_plan_run_quantile(run_plan.handle, n_queries, ptrs, len(cols), _native.ptr(tv),
-                                                    _native.ptr(probs), P, P if probs.dim() == 2 else 0,
-                                                    _native.ptr(index), _native.ptr(value), _native.ptr(mass),
-                                                    _native.ptr(scratch) if scratch is not None else None, flags,
-                                                    _native.stream_ptr(device)), "cbn_plan_run_quantile")
-        return index, value, mass
+    _probs = staticmethod(_probs)
 
     def timing(self):
         """(calls, avg max-pass ms, avg write-pass ms) over the timed calls of every cached plan."""
