@@ -127,6 +127,14 @@ class DirectFactor(ctypes.Structure):
     ]
 
 
+class ParamInfo(ctypes.Structure):
+    """Mirror of ``cbn_param_info`` (include/cbn_amd.h)."""
+
+    _fields_ = [(n, ctypes.c_int32) for n in (
+        "generic", "nc", "n_chunks", "hmax", "mode", "tab", "m1", "parts", "block_threads", "max_blocks",
+        "lds_bytes", "lds_limit")]
+
+
 # name -> (restype, argtypes)
 _SIGNATURES = {
     "cbn_abi_version": (ctypes.c_int, []),
@@ -157,6 +165,7 @@ _SIGNATURES = {
     "cbn_diag_enabled": (ctypes.c_int32, []),
     "cbn_plan_check": (ctypes.c_int, [ctypes.c_void_p]),
     "cbn_plan_flags": (ctypes.c_int32, [ctypes.c_void_p]),
+    "cbn_plan_param_info": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ParamInfo)]),
     "cbn_scale": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p]),
     "cbn_scale_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p,
                                        ctypes.c_int32, ctypes.c_void_p]),
@@ -280,6 +289,14 @@ def check(rc: int, what: str):
     if rc != 0:
         msg = load().cbn_last_error().decode(errors="replace")
         raise NativeError(f"{what} failed (rc={rc}): {msg}")
+
+
+def param_info(handle) -> dict:
+    """``cbn_plan_param_info`` of a parametric plan's handle as a dict: the
+    query kernel the plan's next call launches and its launch shape."""
+    info = ParamInfo()
+    check(load().cbn_plan_param_info(handle, ctypes.byref(info)), "cbn_plan_param_info")
+    return {n: int(getattr(info, n)) for n, _ in ParamInfo._fields_}
 
 
 def require_gpu(device) -> torch.device:

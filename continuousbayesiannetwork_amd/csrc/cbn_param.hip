@@ -1628,6 +1628,7 @@ struct ParamPlan {
     bool tab_ok = false;  // <= kTabIn inputs per factor and nf * kTabIn <= kTabCols: kernarg column table
     bool all_m1 = false;  // every query factor has all its parents observed (M == 1): the M1 kernels
     int parts = 1;        // factor ranges per query group (a plan constant: the product order)
+    bool split_fits = true;  // the split's combine buffer fits the LDS beside `deep` (else 1 part, no override)
     bool lin16 = false;   // linear M1 plan with N >= 16: 16-column chunks (mu once per 16 columns)
     std::vector<int> in_slot;  // [nf][kTabIn] host copy (table mode)
     size_t deep = 0; // dynamic LDS of the deep-model path (query kernel)
@@ -1647,6 +1648,19 @@ struct ParamPlan {
 }  // namespace cbn
 
 namespace {
+// Dynamic LDS of one k_param_query launch: [column table, slot mode]
+// [deep-model scratch] [the split's combine buffer, parts > 1: one NC x 64
+// tile per wave of a full block].  The one place that sizes it: the launch
+// requests it, plan creation checks it against kDynLdsMax and
+// cbn_plan_param_info reports it.  comb_off: the combine buffer's float offset.
+size_t query_lds(const cbn::ParamPlan* pp, int nc, bool tab, int parts, int* comb_off = nullptr) {
+    size_t lds = (tab ? 0 : (size_t)pp->nf * kMaxP * sizeof(InCol)) + pp->deep;
+    lds = (lds + 15) & ~(size_t)15;
+    if (comb_off) *comb_off = (int)(lds / sizeof(float));
+    if (parts > 1) lds += (size_t)(kQThreads / kWave) * nc * kWave * sizeof(float);
+    return lds;
+}
+
 template <int NC, int HMAX, int MODE, bool M1 = false, bool TAB = (MODE < 4)>
 void launch_query_t(const cbn::ParamPlan* pp, unsigned grid, const PEv& ev, long long Q, int QW, int L,
                     unsigned* words, float* out, hipStream_t s, int parts) {
@@ -1663,10 +1677,7 @@ void launch_query_t(const cbn::ParamPlan* pp, unsigned grid, const PEv& ev, long
     sp.ucap = pp->guard_ucap[parts];
     sp.screen = guard ? pp->guard_screen[parts] : 0.f;
     sp.mono = pp->mono && guard ? 1 : 0;
-    size_t lds = (TAB ? 0 : (size_t)pp->nf * kMaxP * sizeof(InCol)) + pp->deep;
-    lds = (lds + 15) & ~(size_t)15;
-    sp.comb_off = (int)(lds / sizeof(float));
-    if (parts > 1) lds += (size_t)(kQThreads / kWave) * NC * kWave * sizeof(float);
+    const size_t lds = query_lds(pp, NC, TAB, parts, &sp.comb_off);
     hipLaunchKernelGGL((k_param_query<NC, HMAX, MODE, TAB, M1>), dim3(grid), dim3(query_block_threads(parts)), lds, s,
                        pp->d_image,
                        pp->cst_off, pp->nf, ev, Q, pp->N, L, QW, pp->max_slots, words, out, sp);
@@ -1681,11 +1692,11 @@ bool specialised(int hmax, int mode) { return mode < 4 && (hmax == 0 || mode >= 
 // (one-hidden-layer plans with every parent observed: the M1 forms)
 template <int NC>
 void launch_query_mlp(const cbn::ParamPlan* pp, unsigned grid, const PEv& ev, long long Q, int QW, int L,
-                      unsigned* words, float* out, hipStream_t s, int parts) {
+                      unsigned* words, float* out, hipStream_t s, int parts, bool m1) {
 #define CBN_Q(H, M, M1) launch_query_t<NC, H, M, M1>(pp, grid, ev, Q, QW, L, words, out, s, parts)
     switch (pp->hmax * 8 + pp->mode) {
-        case 1 * 8 + 2: if (pp->all_m1) CBN_Q(1, 2, true); else CBN_Q(1, 2, false); break;
-        case 1 * 8 + 3: if (pp->all_m1) CBN_Q(1, 3, true); else CBN_Q(1, 3, false); break;
+        case 1 * 8 + 2: if (m1) CBN_Q(1, 2, true); else CBN_Q(1, 2, false); break;
+        case 1 * 8 + 3: if (m1) CBN_Q(1, 3, true); else CBN_Q(1, 3, false); break;
         case 32 * 8 + 2: CBN_Q(32, 2, false); break;
         default: CBN_Q(32, 3, false); break;
     }
@@ -1702,6 +1713,56 @@ void launch_query_lin(const cbn::ParamPlan* pp, unsigned grid, const PEv& ev, lo
         case 2: launch_query_t<NCL, 0, 2, M1>(pp, grid, ev, Q, QW, L, words, out, s, parts); break;
         default: launch_query_t<NCL, 0, 3, M1>(pp, grid, ev, Q, QW, L, words, out, s, parts); break;
     }
+}
+
+// The query kernel a call of the plan launches and its launch shape: what
+// plan creation fixed plus what is read per call (the CBN_PARAM_LIN8 /
+// CBN_PARAM_PARTS overrides under CBN_DIAG, the order guard's veto).  Plan
+// constants and the process environment only -- never the batch -- so a row's
+// bits do not depend on how a batch is sharded.  param_run dispatches on it
+// and cbn_plan_param_info reports it.
+struct ParamSel {
+    bool generic, tab, m1;
+    int nc, L, hmax, mode, parts, block_threads;
+    size_t lds;
+};
+
+ParamSel param_select(const cbn::ParamPlan* pp) {
+    ParamSel v;
+    memset(&v, 0, sizeof(v));
+    if (pp->generic) {  // k_param_query_gen: thread per (query, chunk), two LDS activation buffers per thread
+        v.generic = true;
+        v.nc = kGenNC;
+        v.L = (pp->N + kGenNC - 1) / kGenNC;
+        v.mode = 4;
+        v.parts = 1;
+        v.block_threads = pp->gT;
+        v.lds = (size_t)2 * pp->wbuf * pp->gT * sizeof(float);
+        return v;
+    }
+    const bool spec = specialised(pp->hmax, pp->mode);
+    // column chunk: linear models (mu costs a few FMAs) take 8 columns per lane
+    // (<= 64 VGPRs: 8 waves per SIMD); MLPs keep whole rows up to 32 columns
+    // (every extra chunk re-evaluates the network)
+    v.nc = pp->nc;
+    const bool lin16 = pp->lin16 && !diag_env("CBN_PARAM_LIN8");
+    if (pp->hmax == 0 && spec) v.nc = lin16 ? 16 : 8;
+    v.L = (pp->N + v.nc - 1) / v.nc;
+    // factor split (ParamPlan::parts; CBN_PARAM_PARTS overrides it for A/B)
+    v.parts = pp->parts;
+    if (const char* e = diag_env("CBN_PARAM_PARTS")) {
+        const int p = atoi(e);
+        if (p == 1 || p == 2 || p == 3 || p == 4 || p == 6) v.parts = p;
+    }
+    if (!pp->guard_ok[v.parts]) v.parts = 1;  // a range whose products could overflow: the reference's order only
+    if (!pp->split_fits) v.parts = 1;         // no LDS for the combine buffer beside the deep-model scratch
+    v.block_threads = query_block_threads(v.parts);
+    v.hmax = spec ? pp->hmax : 32;  // (the per-factor-switch kernel is the one <16, 32, 4> instantiation)
+    v.mode = spec ? pp->mode : 4;
+    v.tab = spec;
+    v.m1 = spec && (pp->hmax == 0 ? lin16 || pp->all_m1 : pp->hmax == 1 && pp->all_m1);
+    v.lds = query_lds(pp, v.nc, v.tab, v.parts);
+    return v;
 }
 }  // namespace
 
@@ -1733,12 +1794,13 @@ int cbn::param_run(cbn_plan* plan, int64_t n_queries, const float* const* eviden
     } else {
         for (int i = 0; i < n_evidence; ++i) ev.p[i] = evidence[i];
     }
-    if (pp->generic) {
+    const ParamSel sel = param_select(pp);
+    if (sel.generic) {
         for (int i = 0; i < n_evidence; ++i) ev.p[i] = evidence[i];
-        const int L = (pp->N + kGenNC - 1) / kGenNC;
+        const int L = sel.L;
         const long long tasks = n_queries * L;
         long long grid = std::max(1LL, std::min((tasks + pp->gT - 1) / pp->gT, (long long)pp->max_slots));
-        const size_t lds = (size_t)2 * pp->wbuf * pp->gT * sizeof(float);
+        const size_t lds = sel.lds;
         allow_deep(&k_param_query_gen);
         const bool raw = (flags & CBN_RUN_RAW) != 0;
         unsigned* words = raw ? max_bits : plan->d_sync + kMaxWordOff;
@@ -1750,39 +1812,27 @@ int cbn::param_run(cbn_plan* plan, int64_t n_queries, const float* const* eviden
         return launch_scale(out, n_queries * (long long)pp->N, words, pp->max_slots, max_bits, s);
     }
     const long long QW = (n_queries + kWave - 1) / kWave;
-    // column chunk: linear models (mu costs a few FMAs) take 8 columns per lane
-    // (<= 64 VGPRs: 8 waves per SIMD); MLPs keep whole rows up to 32 columns
-    // (every extra chunk re-evaluates the network)
-    int nc = pp->nc;
-    const bool lin16 = pp->lin16 && !diag_env("CBN_PARAM_LIN8");
-    if (pp->hmax == 0 && specialised(pp->hmax, pp->mode)) nc = lin16 ? 16 : 8;
-    const int L = (pp->N + nc - 1) / nc;
+    // the variant (column chunk, factor split, M1 form): param_select
+    const int nc = sel.nc, L = sel.L, parts = sel.parts;
     const long long waves = QW * L;
     if (waves >= (1LL << 31) || n_queries > (1LL << 30))
         return set_err(CBN_E_LIMIT, "cbn_plan_run: batch too large for one launch");
-    // factor split (ParamPlan::parts; CBN_PARAM_PARTS overrides it for A/B)
-    int parts = pp->parts;
-    if (const char* e = diag_env("CBN_PARAM_PARTS")) {
-        const int v = atoi(e);
-        if (v == 1 || v == 2 || v == 3 || v == 4 || v == 6) parts = v;
-    }
-    if (!pp->guard_ok[parts]) parts = 1;  // a range whose products could overflow: the reference's order only
-    const int wpb = query_block_threads(parts) / kWave;
+    const int wpb = sel.block_threads / kWave;
     long long grid = (waves * parts + wpb - 1) / wpb;
     grid = std::max(1LL, std::min(grid, (long long)pp->max_slots));
     const bool raw = (flags & CBN_RUN_RAW) != 0;
     unsigned* words = raw ? max_bits : plan->d_sync + kMaxWordOff;
-    if (!specialised(pp->hmax, pp->mode)) {
+    if (!sel.tab) {
         launch_query_t<16, 32, 4>(pp, (unsigned)grid, ev, n_queries, (int)QW, L, words, out, s, parts);
-    } else if (pp->hmax == 0) {  // linear models: 8-column chunks
-        if (lin16) launch_query_lin<16, true>(pp, (unsigned)grid, ev, n_queries, (int)QW, L, words, out, s, parts);
-        else if (pp->all_m1) launch_query_lin<8, true>(pp, (unsigned)grid, ev, n_queries, (int)QW, L, words, out, s, parts);
+    } else if (sel.hmax == 0) {  // linear models: 8- or 16-column chunks
+        if (nc == 16) launch_query_lin<16, true>(pp, (unsigned)grid, ev, n_queries, (int)QW, L, words, out, s, parts);
+        else if (sel.m1) launch_query_lin<8, true>(pp, (unsigned)grid, ev, n_queries, (int)QW, L, words, out, s, parts);
         else launch_query_lin<8, false>(pp, (unsigned)grid, ev, n_queries, (int)QW, L, words, out, s, parts);
     } else {
         switch (nc) {
-            case 8: launch_query_mlp<8>(pp, (unsigned)grid, ev, n_queries, (int)QW, L, words, out, s, parts); break;
-            case 16: launch_query_mlp<16>(pp, (unsigned)grid, ev, n_queries, (int)QW, L, words, out, s, parts); break;
-            default: launch_query_mlp<32>(pp, (unsigned)grid, ev, n_queries, (int)QW, L, words, out, s, parts); break;
+            case 8: launch_query_mlp<8>(pp, (unsigned)grid, ev, n_queries, (int)QW, L, words, out, s, parts, sel.m1); break;
+            case 16: launch_query_mlp<16>(pp, (unsigned)grid, ev, n_queries, (int)QW, L, words, out, s, parts, sel.m1); break;
+            default: launch_query_mlp<32>(pp, (unsigned)grid, ev, n_queries, (int)QW, L, words, out, s, parts, sel.m1); break;
         }
     }
     PHIP_TRY(hipGetLastError());
@@ -2098,10 +2148,6 @@ int cbn_plan_create_param(const cbn_param_factor* factors, int32_t n_factors, in
     } else {
         pp->mode = 4;  // the slot-mode (LDS column table) kernel is the generic one
     }
-    if ((size_t)n_factors * kMaxP * sizeof(InCol) + pp->deep > (size_t)kDynLdsMax) {
-        delete pp;
-        return set_err(CBN_E_LIMIT, "parametric plan: %d factors need more LDS than a CU has", n_factors);
-    }
     // column chunk per lane: whole rows when they fit (the model runs once
     // per query and factor), else 32-column chunks
     int nc = 32;
@@ -2117,6 +2163,23 @@ int cbn_plan_create_param(const cbn_param_factor* factors, int32_t n_factors, in
     }
     pp->nc = nc;
     pp->L = (N + nc - 1) / nc;
+    {   // The split's combine buffer (nc x 2 KiB) shares the dynamic LDS with
+        // the deep-model scratch (128 KiB for a network of >= 2 hidden
+        // layers) and the slot-mode column table: where the three exceed
+        // what a launch may request, the plan runs one part -- a plan
+        // constant like `parts`, no override undoes it (param_select) -- and
+        // a plan that does not fit even so is refused here, not at its first
+        // call.  (Linear plans launch 8 or 16 columns whatever `nc` says;
+        // they have no scratch, and 16 bounds both.)
+        const bool spec = specialised(pp->hmax, pp->mode);
+        const int lnc = spec && pp->hmax == 0 ? 16 : nc;
+        pp->split_fits = query_lds(pp, lnc, spec, 2) <= (size_t)kDynLdsMax;
+        if (!pp->split_fits) pp->parts = 1;
+        if (query_lds(pp, lnc, spec, pp->parts) > (size_t)kDynLdsMax) {
+            delete pp;
+            return set_err(CBN_E_LIMIT, "parametric plan: %d factors need more LDS than a CU has", n_factors);
+        }
+    }
     pp->max_slots = std::min(4 * num_cu(), kMaxSlots);
     {   // factor ranges of the split query kernel, balanced by estimated VALU cost
         std::vector<double> cost(n_factors, 1.0);
@@ -2219,6 +2282,26 @@ int cbn_plan_create_param(const cbn_param_factor* factors, int32_t n_factors, in
         return set_err(CBN_E_HIP, "cbn_plan_create_param: device allocation/upload/build failed");
     }
     *plan = P;
+    return CBN_OK;
+}
+
+int cbn_plan_param_info(const cbn_plan* plan, cbn_param_info* out) {
+    if (!plan || !out) return set_err(CBN_E_ARG, "cbn_plan_param_info: null argument");
+    if (!plan->param) return set_err(CBN_E_ARG, "cbn_plan_param_info: not a parametric plan");
+    const ParamPlan* pp = plan->param;
+    const ParamSel v = param_select(pp);
+    out->generic = v.generic ? 1 : 0;
+    out->nc = v.nc;
+    out->n_chunks = v.L;
+    out->hmax = v.hmax;
+    out->mode = v.mode;
+    out->tab = v.tab ? 1 : 0;
+    out->m1 = v.m1 ? 1 : 0;
+    out->parts = v.parts;
+    out->block_threads = v.block_threads;
+    out->max_blocks = pp->max_slots;
+    out->lds_bytes = (int32_t)v.lds;
+    out->lds_limit = kDynLdsMax;
     return CBN_OK;
 }
 

@@ -411,6 +411,32 @@ int cbn_plan_check(cbn_plan* plan);
 #define CBN_PLAN_QUANTILE 4096 /* cbn_plan_run_quantile runs in the query kernel itself */
 int32_t cbn_plan_flags(const cbn_plan* plan);
 
+/* Which parametric query kernel the next cbn_plan_run of the plan launches,
+ * and with what launch shape: the values the launch itself uses (one host
+ * selection serves both), read-only.  Plans with CBN_PLAN_PARAMETRIC only
+ * (CBN_E_ARG otherwise, and for NULL arguments).
+ *   generic       1: k_param_query_gen (models beyond the register-resident
+ *                 kernels); hmax / tab / m1 are 0, mode 4 and parts 1 then
+ *   nc, n_chunks  output columns per lane and column chunks per query
+ *   hmax, mode, tab, m1
+ *                 k_param_query's template arguments HMAX (0 linear, 1 one
+ *                 hidden layer, 32 deeper), MODE (0 / 1 Gaussian with unit /
+ *                 other sigma, 2 / 3 logistic with unit / other scale, 4 the
+ *                 per-factor switch), TAB (kernel-argument column table) and
+ *                 M1 (every query factor has all its parents observed)
+ *   parts         factor ranges per query group (1: no split)
+ *   block_threads, max_blocks
+ *                 threads per block and the grid's upper bound (larger
+ *                 batches make further trips of the grid-stride loop)
+ *   lds_bytes     dynamic LDS the query launch requests (deep-model scratch,
+ *                 column table, the split's combine buffer)
+ *   lds_limit     the most a launch may request
+ * Added in ABI 5 (additive).  No reference counterpart. */
+typedef struct cbn_param_info {
+    int32_t generic, nc, n_chunks, hmax, mode, tab, m1, parts, block_threads, max_blocks, lds_bytes, lds_limit;
+} cbn_param_info;
+int cbn_plan_param_info(const cbn_plan* plan, cbn_param_info* out);
+
 /* Test hook: mark the plan as if a single-launch call had timed out in its
  * grid barrier, so the next cbn_plan_run returns CBN_E_TIMEOUT (exercises the
  * reporting path without starving the GPU).  No reference counterpart. */

@@ -11,6 +11,8 @@ the environment it is testing.  Prints one JSON line.
     python tests/diag_child.py gridfull  # configs[4] bench batch: k_query_slots vs k_query_fast (CBN_NO_SLOTS)
     python tests/diag_child.py gridcoal  # k_query_slots' coalesced index phase vs the per-lane one (CBN_SLOTS_NO_COAL)
     python tests/diag_child.py coalspecial  # special evidence values: coalesced index phase (CBN_SLOTS_COAL) vs per-lane
+    python tests/diag_child.py paramlin  # linear parametric plan: 16- vs 8-column chunks, M1 vs CBN_PARAM_NO_M1
+    python tests/diag_child.py paramh1   # NN [16] plan: CBN_PARAM_NC 8 / 16 / 32, M1 vs CBN_PARAM_NO_M1
 """
 import json
 import os
@@ -132,6 +134,50 @@ def main(mode: str):
             res["equal_raw"].append(bool(np.array_equal(raws[0].view(np.uint32), raws[1].view(np.uint32))))
             keep[tag] = outs[1]
         np.savez(os.environ["CBN_CHILD_OUT"], **keep)
+    elif mode in ("paramlin", "paramh1"):
+        # one parametric plan (tests/param_matrix.py DIAG_CASES, N = 40, all
+        # evidence) under the CBN_PARAM_* switches: per setting the plan is
+        # rebuilt (CBN_PARAM_NC / NO_M1 are read at plan creation, LIN8 /
+        # PARTS per call), its cbn_plan_param_info recorded and its raw rows
+        # compared bit for bit with the first setting of its group -- within
+        # a group the factor split (parts) is the same, across groups it is
+        # not, and the association of the product differs by design
+        import tempfile
+
+        import param_matrix as pm
+        from test_gpu_param import load_fixture_params
+
+        case = pm.DIAG_CASES[mode[5:]]
+        data, cols, edges, target, _, params = pm.network(case)
+        bn = make_bn(BayesianNetwork, edges, cols, data, device=dev, estimator=case.est,
+                     config=param_config(case.est, n_epochs=1, model=case.model))
+        with tempfile.TemporaryDirectory() as tmp:
+            load_fixture_params(bn, {"meta": {"estimator": case.est}, "params": params}, tmp, dev)
+        ev = {k: torch.tensor(v, device=dev) for k, v in pm.evidence(case, pm.SMALL).items()}
+        if mode == "paramlin":  # (a linear plan launches 8 or 16 columns whatever CBN_PARAM_NC says: LIN8 picks 8)
+            groups = [[{}, {"CBN_PARAM_LIN8": "1"}],
+                      [{"CBN_PARAM_PARTS": "2"}, {"CBN_PARAM_PARTS": "2", "CBN_PARAM_LIN8": "1"},
+                       {"CBN_PARAM_PARTS": "2", "CBN_PARAM_NO_M1": "1"}]]
+        else:
+            groups = [[{"CBN_PARAM_NC": "32"}, {"CBN_PARAM_NC": "16"}, {"CBN_PARAM_NC": "8"}],
+                      [{"CBN_PARAM_PARTS": "2"}, {"CBN_PARAM_PARTS": "2", "CBN_PARAM_NO_M1": "1"},
+                       {"CBN_PARAM_PARTS": "2", "CBN_PARAM_NO_M1": "1", "CBN_PARAM_NC": "16"}]]
+        res["infos"], res["equal"], res["finite"] = [], [], []
+        names = ("CBN_PARAM_NC", "CBN_PARAM_NO_M1", "CBN_PARAM_LIN8", "CBN_PARAM_PARTS")
+        for group in groups:
+            first = None
+            for env in group:
+                for n in names:
+                    os.environ.pop(n, None)
+                os.environ.update(env)
+                bn.engine.invalidate()
+                plan, _ = bn.engine.call_plan(target, ev, case.N)
+                info = _native.param_info(plan.handle)
+                raw = bn.engine.infer_raw(target, ev, case.N)[0].cpu().numpy().copy()
+                first = raw if first is None else first
+                res["infos"].append({k: info[k] for k in ("nc", "n_chunks", "hmax", "mode", "m1", "parts")})
+                res["equal"].append(bool(np.array_equal(raw.view(np.uint32), first.view(np.uint32))))
+                res["finite"].append(bool(np.isfinite(raw).all() and (raw > 0).any(1).all()))
     print(json.dumps(res))
 
 

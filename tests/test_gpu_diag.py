@@ -115,3 +115,38 @@ def test_special_evidence_through_coalesced_index_phase(gpu, tmp_path):
             r_neg, r_pos = (next(r[0] for r in rows if r[1] == c and r[2] == k) for k in (4, 5))
             np.testing.assert_array_equal(p[r_neg].view(np.uint32), p[r_pos].view(np.uint32))
         assert any((p[r[0]] > 0).any() for r in rows if r[4])
+
+
+def _info(nc, hmax, mode, m1, parts, N=40):
+    return {"nc": nc, "n_chunks": -(-N // nc), "hmax": hmax, "mode": mode, "m1": m1, "parts": parts}
+
+
+def test_linear_param_rows_do_not_depend_on_chunk_width_or_m1_form(gpu):
+    """One LinearRegression plan (sigma = 0.5, 8 factors, N = 40, all
+    evidence; tests/param_matrix.py) under CBN_DIAG=1: the 16-column kernel
+    and the 8-column one (CBN_PARAM_LIN8) give bit-identical raw rows at 4
+    parts, and at 2 parts (CBN_PARAM_PARTS=2) so do both and the
+    M1 = false kernel (CBN_PARAM_NO_M1) -- a column's arithmetic does not
+    depend on its chunk, and lin4's zero-padded fma chain is model_mu<0>'s
+    (cbn_param.hip: fma(0, 0, s) == s), with mul_row_t behind both.  A linear
+    plan has no 32-column instantiation, and CBN_PARAM_NC does not reach it.
+    Rows are not compared across `parts`: the product's association differs
+    by design."""
+    res, _ = _child("paramlin", CBN_DIAG="1")
+    assert res["diag"] == 1
+    assert res["infos"] == [_info(16, 0, 1, 1, 4), _info(8, 0, 1, 1, 4),
+                            _info(16, 0, 1, 1, 2), _info(8, 0, 1, 1, 2), _info(8, 0, 1, 0, 2)]
+    assert res["equal"] == [True] * 5 and res["finite"] == [True] * 5
+
+
+def test_mlp_param_rows_do_not_depend_on_chunk_width_or_m1_form(gpu):
+    """One NN [16] tanh plan (scale 0.5, 9 factors, N = 40, all evidence)
+    under CBN_DIAG=1: CBN_PARAM_NC = 32, 16 and 8 (2, 3 and 5 chunks) give
+    bit-identical raw rows at the plan's 4 parts; at 2 parts the M1 kernel,
+    the M1 = false one (CBN_PARAM_NO_M1: both evaluate the pair-packed
+    mlp1p forms and mul_row_t) and the latter at 16 columns do too."""
+    res, _ = _child("paramh1", CBN_DIAG="1")
+    assert res["diag"] == 1
+    assert res["infos"] == [_info(32, 1, 3, 1, 4), _info(16, 1, 3, 1, 4), _info(8, 1, 3, 1, 4),
+                            _info(32, 1, 3, 1, 2), _info(32, 1, 3, 0, 2), _info(16, 1, 3, 0, 2)]
+    assert res["equal"] == [True] * 6 and res["finite"] == [True] * 6

@@ -4,6 +4,8 @@ import ctypes
 import os
 import re
 
+import pytest
+
 from continuousbayesiannetwork_amd import _native
 
 HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "cbn_amd.h")
@@ -37,6 +39,44 @@ def test_abi_version_and_struct_layout():
     assert ctypes.sizeof(_native.CpdRef) == 8 + 5 * 8 + 8
     # cbn_direct_factor: 2 int32 + 3 pointers + cpd
     assert ctypes.sizeof(_native.DirectFactor) == 8 + 3 * 8 + ctypes.sizeof(_native.CpdRef) + 8
+    # cbn_param_info: 12 int32, in the header's order
+    assert ctypes.sizeof(_native.ParamInfo) == 4 * 12
+    src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    body = re.search(r"typedef struct cbn_param_info \{(.*?)\} cbn_param_info;", src, flags=re.S).group(1)
+    assert [w.strip() for w in body.replace("int32_t", "").replace(";", "").split(",")] == \
+        [n for n, _ in _native.ParamInfo._fields_]
+
+
+def test_param_info_argument_errors_are_reported_without_gpu():
+    """cbn_plan_param_info refuses null arguments before it reads either."""
+    lib = _native.load()
+    info = _native.ParamInfo()
+    assert lib.cbn_plan_param_info(None, ctypes.byref(info)) == _native.CBN_E_ARG
+    assert b"null argument" in lib.cbn_last_error()
+    assert lib.cbn_plan_param_info(None, None) == _native.CBN_E_ARG
+
+
+@pytest.mark.gpu
+def test_param_info_refuses_a_table_plan(gpu):
+    """A BruteForce (table) plan is not parametric: CBN_E_ARG with a null
+    output too, and the output struct is left untouched."""
+    import torch
+
+    from continuousbayesiannetwork_amd import BayesianNetwork
+    from helpers import chain_data, make_bn, sample_evidence
+
+    data, cols, edges = chain_data(4, 4, 2000, 1)
+    bn = make_bn(BayesianNetwork, edges, cols, data, device=gpu)
+    ev = {k: torch.tensor(v, device=gpu) for k, v in sample_evidence(data, cols, cols[:-1], 8, 2).items()}
+    bn.infer(cols[-1], ev, N_max=4)
+    lib = _native.load()
+    plans = list(bn.engine._plans.values())
+    assert plans and not any(lib.cbn_plan_flags(p.handle) & _native.CBN_PLAN_PARAMETRIC for p in plans)
+    info = _native.ParamInfo()
+    info.nc = -7
+    assert lib.cbn_plan_param_info(plans[0].handle, ctypes.byref(info)) == _native.CBN_E_ARG
+    assert b"not a parametric plan" in lib.cbn_last_error() and info.nc == -7
+    assert lib.cbn_plan_param_info(plans[0].handle, None) == _native.CBN_E_ARG
 
 
 def test_argument_errors_are_reported_without_gpu():
