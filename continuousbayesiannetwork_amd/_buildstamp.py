@@ -25,7 +25,8 @@ HOST_FLAGS = ["-O2", "-std=c++17", "-fPIC", "-shared", "-DTORCH_EXTENSION_NAME=_
               "-DTORCH_API_INCLUDE_EXTENSION_H", "-D__HIP_PLATFORM_AMD__=1", "-DUSE_ROCM=1"]
 
 LIB_SOURCES = [os.path.join(CSRC, f) for f in ("cbn_infer.hip", "cbn_param.hip", "cbn_direct.hip")]
-LIB_HEADERS = [os.path.join(CSRC, "cbn_internal.h"), os.path.join(ROOT, "include", "cbn_amd.h")]
+LIB_HEADERS = [os.path.join(CSRC, "cbn_internal.h"), os.path.join(CSRC, "cbn_table_plan.h"),
+               os.path.join(ROOT, "include", "cbn_amd.h")]
 HOST_SOURCES = [os.path.join(CSRC, "host_fast.cpp")]
 
 

@@ -33,7 +33,7 @@ def lib_path() -> str:
 
 LIB_PATH = lib_path()
 
-ABI_VERSION = 5
+ABI_VERSION = 6
 CBN_MAX_PARENTS = 8
 CBN_MAX_DIRECT_PARENTS = 32
 CBN_MAX_EVIDENCE = 256
@@ -135,6 +135,17 @@ class ParamInfo(ctypes.Structure):
         "lds_bytes", "lds_limit")]
 
 
+class TablePlanInfo(ctypes.Structure):
+    """Mirror of ``struct cbn_table_plan_info`` (include/cbn_amd.h)."""
+
+    _fields_ = [(n, ctypes.c_int32) for n in (
+        "struct_bytes", "flags", "kernel", "vpl", "lanes", "row_stride", "prefix", "lds_tab_floats", "lds_bytes",
+        "blocks_per_cu", "max_slots", "fused_candidate")] + [
+        ("table_bytes", ctypes.c_int64), ("fused_capacity", ctypes.c_int64)]
+
+
+TABLE_KERNELS = ("generic", "fast", "paired_fast", "staged", "cols", "slots")  # CBN_TABLE_KERNEL_*
+
 # name -> (restype, argtypes)
 _SIGNATURES = {
     "cbn_abi_version": (ctypes.c_int, []),
@@ -166,6 +177,8 @@ _SIGNATURES = {
     "cbn_plan_check": (ctypes.c_int, [ctypes.c_void_p]),
     "cbn_plan_flags": (ctypes.c_int32, [ctypes.c_void_p]),
     "cbn_plan_param_info": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ParamInfo)]),
+    "cbn_table_plan_info": (ctypes.c_int, [ctypes.POINTER(FactorDesc), ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                           ctypes.POINTER(TablePlanInfo)]),
     "cbn_scale": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p]),
     "cbn_scale_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p,
                                        ctypes.c_int32, ctypes.c_void_p]),
@@ -297,6 +310,15 @@ def param_info(handle) -> dict:
     info = ParamInfo()
     check(load().cbn_plan_param_info(handle, ctypes.byref(info)), "cbn_plan_param_info")
     return {n: int(getattr(info, n)) for n, _ in ParamInfo._fields_}
+
+
+def table_plan_info(descs, n_factors: int, n_samples: int, n_cu: int) -> dict:
+    """``cbn_table_plan_info`` as a dict: what ``cbn_plan_create`` would decide
+    for these descriptors on a device of ``n_cu`` CUs.  Needs no GPU."""
+    info = TablePlanInfo()
+    info.struct_bytes = ctypes.sizeof(TablePlanInfo)
+    check(load().cbn_table_plan_info(descs, n_factors, n_samples, n_cu, ctypes.byref(info)), "cbn_table_plan_info")
+    return {n: int(getattr(info, n)) for n, _ in TablePlanInfo._fields_}
 
 
 def require_gpu(device) -> torch.device:

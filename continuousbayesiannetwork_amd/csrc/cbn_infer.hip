@@ -36,8 +36,10 @@
 #include <unistd.h>  // environ
 
 #include "cbn_internal.h"
+#include "cbn_table_plan.h"
 
 using namespace cbn;
+using namespace cbn::table;
 
 namespace {
 thread_local std::string g_err;
@@ -72,40 +74,6 @@ int cbn::set_err(int code, const char* fmt, ...) {
     return code;
 }
 
-namespace cbn {
-// Device-side factor descriptor (built once per plan, read with wave-uniform
-// indices so the compiler keeps it on the scalar path).
-struct DevFactor {
-    int kind;
-    int n_parents;
-    int node_card;
-    int n_free;
-    int parent_card[CBN_MAX_PARENTS];
-    int ev_slot[CBN_MAX_PARENTS];
-    int cpd_stride[CBN_MAX_PARENTS];
-    const float* cpd;
-    const int* node_sample_idx;
-    const int* parent_sample_idx;
-    int table_off;   // float offset of this factor's table ([rows][RS]) in the image
-    int rows;        // prod(card of observed parents) (QUERY) or 1
-    int n_entries;   // rows * N
-    int free_combos; // N^n_free
-    int wave_mode;   // build kernel: 1 = one wave per entry (many free combos)
-};
-
-struct QSlot {
-    int dom_off;  // float offset of the sorted domain in the image
-    int card;
-    int dense;    // 1: domain is exactly {0, 1, ..., card-1} -> index = value
-    int pad;
-};
-
-struct BuildItem {
-    int factor;
-    int unit_begin;
-};
-}  // namespace cbn
-
 namespace {
 
 #define HIP_TRY(expr)                                                                     \
@@ -115,8 +83,6 @@ namespace {
             return set_err(CBN_E_HIP, "%s failed: %s", #expr, hipGetErrorString(_e));     \
     } while (0)
 
-constexpr int kMaxP = CBN_MAX_PARENTS;
-constexpr int kQueryThreads = 1024;
 constexpr int kBuildThreads = 256;
 
 struct EvPtrs {
@@ -132,10 +98,6 @@ struct EvPtrs {
 // kTagNone = no observed parent (a valid dummy column, read at row 0), so the
 // first-parent loads of all a lane's factors issue back to back, unbranched.
 constexpr uintptr_t kTagMore = 1, kTagNone = 2;
-// Kernel arguments are copied per launch: plans of <= 32 factors (configs[1],
-// [2]) take a 1 KiB table (launch 3.2 us of host time instead of 4.9 us with
-// the 3.3 KiB one, profiles/r01_launch_cost.txt).
-constexpr int kFastPtrsSmall = 128;
 template <int NP>
 struct FPtrsT {
     const float* p[NP];
@@ -826,7 +788,6 @@ __global__ void __launch_bounds__(256) k_merge_prefix(float* __restrict__ image,
     *t = v * *t;
 }
 
-constexpr int kFqInts = 4 + 2 * kMaxP;  // img_off, kind, n_obs, pad, obs_slot[], obs_card[]
 constexpr int kUnroll = 4;
 
 __device__ __forceinline__ int slot_index(const float* __restrict__ img, const QSlot& sl, float x) {
@@ -997,21 +958,7 @@ k_query(const DevFactor* __restrict__ fac, int nf, const QSlot* __restrict__ slo
     }
 }
 
-constexpr int kFastObs = 4;  // fast path: observed parents per factor
-
-
-// Per-factor static record, written into the plan image at plan creation and
-// copied to LDS with the tables (one LDS-DMA stream, no per-call build).
-struct alignas(16) FastRec {
-    int table_off;
-    int n_obs;
-    int card[kFastObs];     // bit 30: domain is {0..card-1} (index = value)
-    int dom_off[kFastObs];
-    int slot[kFastObs];
-    int pad[2];
-};
-constexpr int kDenseBit = 1 << 30;
-constexpr int kRecFloats = sizeof(FastRec) / 4;
+// (kFastObs, FastRec: cbn_table_plan.h)
 
 // Fast path: the L = N / (4 VPL) lanes of one query (a power of two dividing
 // 64, so a query never straddles waves) split its factors: lane l loads the
@@ -1549,13 +1496,7 @@ constexpr int kColKB = CBN_COL_KB;
 // readfirstlane -> branch (3-5 dependent LDS round trips per factor) and
 // gathered through flat loads.  (s_load of this record per factor measured
 // the same.)  configs[2]: X35 27.6 -> 26.7 us, X36 21.6 -> 19.9 us.
-struct alignas(16) ColRec {
-    int base;            // float offset of the table (LDS copy when `lds`, else the image)
-    int n_obs;           // observed parents (<= kFastObs)
-    int par[kFastObs];   // (evidence slot << 24) | row weight in floats (= stride x RS, < 2^24)
-    int lds;             // 1: table is in LDS
-    int pad;
-};
+// (struct ColRec: cbn_table_plan.h)
 constexpr int kColRecInts = sizeof(ColRec) / 4;
 
 template <int VPL, bool USE_LDS, int MODE, int CH>
@@ -1780,9 +1721,6 @@ k_query_cols(int rec_off, int nf, int ns, const float* __restrict__ gimage, int 
 __host__ __device__ __forceinline__ int slots_sidx_stride(int L) {
     return kQueryThreads / L + 2 * (L >= 16 ? 1 : 16 / L);
 }
-#ifndef CBN_SLOTS_FUSED2
-#define CBN_SLOTS_FUSED2 1  // fused single launch up to two block rounds (0: one round, beyond -> raw + scale)
-#endif
 #ifndef CBN_SLOTS_DPP
 #define CBN_SLOTS_DPP 1  // phase B hands the running product on by DPP row shifts (0: ds_bpermute)
 #endif
@@ -2149,7 +2087,6 @@ k_query_slots(int nf, int ns, const float* __restrict__ gimage, int qslot_off, c
 // reference's factor order.  A value outside a factor's domain points at a
 // zero row, slots past the last factor at a ones row (x * 1 is exact), so the
 // loop has no per-factor guards.
-constexpr int kSR = 256;  // queries per block round
 constexpr int kSQ = 128;  // queries per staging unit (two per lane)
 constexpr int kSU = 4;    // staging units per wave per round (nf <= 32 -> nf * 2 / 16 <= 4)
 // Round 0 with the straight-line fill (lds_dma_copy), A/B on the headline, us
@@ -2957,116 +2894,126 @@ FPtrsT<kFastPtrsSmall> slot_ptrs(const cbn_plan* p, const EvPtrs& ev) {
     return sp;
 }
 
-// dynamic LDS of k_query_slots (its layout, in order): the small tables,
-// QSlot[ns], ColRec[nf], slot pointers, sidx[ns][SQ] (int16, SQ = QB + pad),
-// offsets [QB][nf4], wave maxima
-size_t slots_lds_bytes(long long lds_tab_floats, int ns, int nf, int QB) {
-    const size_t nf4 = (size_t)((nf + 3) & ~3);
-    const size_t SQ = (size_t)slots_sidx_stride(kQueryThreads / QB);
-    size_t b = (size_t)lds_tab_floats * 4 + (size_t)ns * sizeof(QSlot) + (size_t)nf * sizeof(ColRec) +
-               (size_t)((ns + 1) & ~1) * sizeof(void*) + ((((size_t)ns * SQ + 7) & ~size_t(7)) * 2) +
-               (size_t)QB * nf4 * 4 + (kQueryThreads / kWave) * 4 + 64;
-    return (b + 15) & ~size_t(15);
+// The plan's kernel variant as compile-time constants: f(VPL, LDS) with
+// std::integral_constant arguments, resolved from the selection once.
+template <class F>
+auto with_variant(const TableSel& sel, F&& f) {
+    using V1 = std::integral_constant<int, 1>;
+    using V2 = std::integral_constant<int, 2>;
+    if (sel.use_lds) return sel.vpl == 2 ? f(V2{}, std::true_type{}) : f(V1{}, std::true_type{});
+    return sel.vpl == 2 ? f(V2{}, std::false_type{}) : f(V1{}, std::false_type{});
 }
 
-// one fast-kernel launch with the pointer table sized to the plan
-template <int VPL, bool LDS, int MODE, int NP>
-void launch_fast_np(const cbn_plan* p, unsigned blocks, hipStream_t s, const EvPtrs& ev, long long Q, int L,
-                    unsigned epoch, const unsigned* max_in, int n_max, unsigned* max_out, float* out,
-                    const ModeOut& mx) {
-    hipLaunchKernelGGL((k_query_fast<VPL, LDS, MODE, NP>), dim3(blocks), dim3(kQueryThreads), p->fast_lds_bytes, s,
-                       p->rec_off, p->nf, p->ns, p->d_image, p->image_floats, fast_ptrs<NP>(p, ev), Q,
-                       (Q + blocks - 1) / blocks, p->N, p->RS, L, p->paired ? 1 : 0, p->d_sync, epoch, max_in, n_max,
-                       max_out, out, p->lds_tab_floats, p->lds_tab_mask[0], p->lds_tab_mask[1], mx);
+template <TableKernel K>
+using KernelTag = std::integral_constant<TableKernel, K>;
+template <int NP>
+using PtrsTag = std::integral_constant<int, NP>;
+
+// The one mapping from a fast-path plan's selection to its kernel
+// instantiation in MODE: f(kernel family, pointer-table size, kernel).  The
+// launch, the occupancy query and the dynamic-LDS attribute go through it and
+// nothing else names an instantiation.
+template <int MODE, class F>
+auto with_kernel(const TableSel& sel, F&& f) {
+    using Small = PtrsTag<kFastPtrsSmall>;
+    return with_variant(sel, [&](auto vpl, auto lds) {
+        constexpr int V = decltype(vpl)::value;
+        constexpr bool LDS = decltype(lds)::value;
+        switch (sel.kernel) {
+            case TableKernel::Staged:  // paired N = 32 layout in LDS (same grid, same words)
+                return f(KernelTag<TableKernel::Staged>{}, Small{}, &k_query_staged<MODE>);
+            case TableKernel::Slots:
+                return f(KernelTag<TableKernel::Slots>{}, Small{}, &k_query_slots<V, MODE>);
+            case TableKernel::Cols:
+                return f(KernelTag<TableKernel::Cols>{}, Small{},
+                         sel.cols_chunk == 16 ? &k_query_cols<V, LDS, MODE, 16> : &k_query_cols<V, LDS, MODE, 40>);
+            default:  // Fast, PairedFast: the pointer table sized to the plan
+                if (sel.ptrs == kFastPtrsSmall)
+                    return f(KernelTag<TableKernel::Fast>{}, Small{}, &k_query_fast<V, LDS, MODE, kFastPtrsSmall>);
+                return f(KernelTag<TableKernel::Fast>{}, PtrsTag<kFastPtrs>{}, &k_query_fast<V, LDS, MODE, kFastPtrs>);
+        }
+    });
 }
 
-template <int VPL, bool LDS, int MODE>
-void launch_fast_k(const cbn_plan* p, unsigned blocks, hipStream_t s, const EvPtrs& ev, long long Q, int L,
-                   unsigned epoch, const unsigned* max_in, int n_max, unsigned* max_out, float* out,
-                   const FoldJob* fold = nullptr, const ModeOut* mxp = nullptr) {
+// ... and a generic plan's k_query instantiation: f(kernel)
+template <bool WRITE, class F>
+auto with_generic_kernel(const cbn_plan* p, F&& f) {
+    if (p->vec == 4) return p->sel.use_lds ? f(&k_query<4, true, WRITE>) : f(&k_query<4, false, WRITE>);
+    return p->sel.use_lds ? f(&k_query<1, true, WRITE>) : f(&k_query<1, false, WRITE>);
+}
+
+// A launch may request up to kLdsBudget of dynamic LDS: the attribute, on every
+// instantiation this plan can launch (its kernel in each mode, or k_query's
+// two passes) and on no other.
+template <int... MODES>
+void allow_plan_lds(const cbn_plan* p, std::integer_sequence<int, MODES...>) {
+    auto allow = [](auto kernel) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  kLdsBudget);
+    };
+    if (p->sel.fast()) {
+        (with_kernel<MODES>(p->sel, [&](auto, auto, auto kernel) { allow(kernel); }), ...);
+    } else {
+        with_generic_kernel<false>(p, allow);
+        with_generic_kernel<true>(p, allow);
+    }
+}
+using AllModes = std::integer_sequence<int, kModeMax, kModeWrite, kModeFused, kModeRaw, kModeArgmax, kModeMoments,
+                                       kModeQuantile>;
+
+// one launch of the plan's fast-path kernel in MODE
+template <int MODE>
+void launch_fast_k(const cbn_plan* p, unsigned blocks, hipStream_t s, const EvPtrs& ev, long long Q, unsigned epoch,
+                   const unsigned* max_in, int n_max, unsigned* max_out, float* out, const FoldJob* fold = nullptr,
+                   const ModeOut* mxp = nullptr) {
     ModeOut mx;  // (read by kModeArgmax / kModeMoments / kModeQuantile only)
     memset(&mx, 0, sizeof(mx));
     if (mxp) mx = *mxp;
-    if (p->staged) {  // paired N = 32 layout in LDS: the staged kernel (same grid, same words)
-        FoldJob fj;
-        memset(&fj, 0, sizeof(fj));
-        if (fold && fold->rows && fold->n4 > 0) {
-            fj = *fold;
-            fj.chunk = (fj.n4 + blocks - 1) / blocks;
+    const int L = p->sel.lanes;
+    const size_t lds_bytes = p->sel.lds_bytes;
+    long long per = (Q + blocks - 1) / blocks;
+    with_kernel<MODE>(p->sel, [&](auto family, auto np, auto kernel) {
+        constexpr TableKernel K = decltype(family)::value;
+        if constexpr (K == TableKernel::Staged) {
+            FoldJob fj;
+            memset(&fj, 0, sizeof(fj));
+            if (fold && fold->rows && fold->n4 > 0) {
+                fj = *fold;
+                fj.chunk = (fj.n4 + blocks - 1) / blocks;
+            }
+            // factors [prefix, nf): the prefix is folded into factor `prefix`'s table
+            hipLaunchKernelGGL(kernel, dim3(blocks), dim3(kQueryThreads), lds_bytes, s, p->d_image, p->image_floats,
+                               p->rec_off + p->prefix * kRecFloats, p->nf - p->prefix, p->zero_off, Q, per, p->d_sync,
+                               epoch, max_in, n_max, max_out, out, fj, fast_ptrs<kFastPtrsSmall>(p, ev, p->prefix), mx);
+        } else if constexpr (K == TableKernel::Slots) {
+            // Coalesced index phase (round 6: 16-B evidence loads per (slot, 4
+            // queries), the block's waves index every query of the round, block
+            // barriers around it) for launches of >= 3 block rounds: the
+            // configs[4] grid at 262 144 queries 316.5-319.1 -> 279.0-280.1 us,
+            // but at 65 536 (the fused launch's two rounds) 66.2-66.4 -> 73.7-74.1
+            // us -- the barriers put the waves in lockstep across the rounds
+            // (MEASUREMENTS.md, round 6).  Needs 16-B aligned columns and every
+            // block's first query a multiple of 4.
+            const int QBs = kQueryThreads / L;
+            int coal = per > 2LL * QBs && !diag_env("CBN_SLOTS_NO_COAL") ? 1 : 0;
+            if (diag_env("CBN_SLOTS_COAL")) coal = 1;
+            for (int i = 0; i < p->ns; ++i) coal &= (reinterpret_cast<uintptr_t>(ev.p[i]) & 15) == 0 ? 1 : 0;
+            if (coal) per = (per + 3) & ~3LL;
+            hipLaunchKernelGGL(kernel, dim3(blocks), dim3(kQueryThreads), lds_bytes, s, p->nf, p->ns, p->d_image,
+                               p->rec_off + p->nf * kRecFloats, p->d_crec, slot_ptrs(p, ev), Q, per, p->N, L, p->d_sync,
+                               epoch, max_in, n_max, max_out, out, p->lds_tab_floats, p->lds_tab_mask[0],
+                               p->lds_tab_mask[1], coal, mx);
+        } else if constexpr (K == TableKernel::Cols) {
+            hipLaunchKernelGGL(kernel, dim3(blocks), dim3(kQueryThreads), lds_bytes, s, p->rec_off, p->nf, p->ns,
+                               p->d_image, p->image_floats, slot_ptrs(p, ev), Q, per, p->N, p->RS, L, p->d_sync, epoch,
+                               max_in, n_max, max_out, out, p->lds_tab_floats, p->d_crec, mx);
+        } else {
+            hipLaunchKernelGGL(kernel, dim3(blocks), dim3(kQueryThreads), lds_bytes, s, p->rec_off, p->nf, p->ns,
+                               p->d_image, p->image_floats, fast_ptrs<decltype(np)::value>(p, ev), Q, per, p->N, p->RS, L,
+                               p->sel.kernel == TableKernel::PairedFast ? 1 : 0, p->d_sync, epoch, max_in, n_max,
+                               max_out, out, p->lds_tab_floats, p->lds_tab_mask[0], p->lds_tab_mask[1], mx);
         }
-        // factors [prefix, nf): the prefix is folded into factor `prefix`'s table
-        hipLaunchKernelGGL((k_query_staged<MODE>), dim3(blocks), dim3(kQueryThreads), p->staged_lds_bytes, s,
-                           p->d_image, p->image_floats, p->rec_off + p->prefix * kRecFloats, p->nf - p->prefix,
-                           p->zero_off, Q, (Q + blocks - 1) / blocks, p->d_sync, epoch, max_in, n_max, max_out, out,
-                           fj, fast_ptrs<kFastPtrsSmall>(p, ev, p->prefix), mx);
-        return;
-    }
-    if (p->slots) {
-        // Coalesced index phase (round 6: 16-B evidence loads per (slot, 4
-        // queries), the block's waves index every query of the round, block
-        // barriers around it) for launches of >= 3 block rounds: the
-        // configs[4] grid at 262 144 queries 316.5-319.1 -> 279.0-280.1 us,
-        // but at 65 536 (the fused launch's two rounds) 66.2-66.4 -> 73.7-74.1
-        // us -- the barriers put the waves in lockstep across the rounds
-        // (MEASUREMENTS.md, round 6).  Needs 16-B aligned columns and every
-        // block's first query a multiple of 4.
-        const int QBs = kQueryThreads / L;
-        long long per = (Q + blocks - 1) / blocks;
-        int coal = per > 2LL * QBs && !diag_env("CBN_SLOTS_NO_COAL") ? 1 : 0;
-        if (diag_env("CBN_SLOTS_COAL")) coal = 1;
-        for (int i = 0; i < p->ns; ++i) coal &= (reinterpret_cast<uintptr_t>(ev.p[i]) & 15) == 0 ? 1 : 0;
-        if (coal) per = (per + 3) & ~3LL;
-        hipLaunchKernelGGL((k_query_slots<VPL, MODE>), dim3(blocks), dim3(kQueryThreads), p->fast_lds_bytes, s, p->nf,
-                           p->ns, p->d_image, p->rec_off + p->nf * kRecFloats, p->d_crec, slot_ptrs(p, ev), Q, per,
-                           p->N, L, p->d_sync, epoch, max_in, n_max, max_out, out, p->lds_tab_floats,
-                           p->lds_tab_mask[0], p->lds_tab_mask[1], coal, mx);
-        return;
-    }
-    if (p->cols) {
-        auto k = (p->ns + L - 1) / L <= 16 ? k_query_cols<VPL, LDS, MODE, 16> : k_query_cols<VPL, LDS, MODE, 40>;
-        hipLaunchKernelGGL(k, dim3(blocks), dim3(kQueryThreads), p->fast_lds_bytes, s,
-                           p->rec_off, p->nf, p->ns, p->d_image, p->image_floats, slot_ptrs(p, ev), Q,
-                           (Q + blocks - 1) / blocks, p->N, p->RS, L, p->d_sync, epoch, max_in, n_max, max_out, out,
-                           p->lds_tab_floats, p->d_crec, mx);
-        return;
-    }
-    if (p->nf * kFastObs <= kFastPtrsSmall)
-        launch_fast_np<VPL, LDS, MODE, kFastPtrsSmall>(p, blocks, s, ev, Q, L, epoch, max_in, n_max, max_out, out, mx);
-    else
-        launch_fast_np<VPL, LDS, MODE, kFastPtrs>(p, blocks, s, ev, Q, L, epoch, max_in, n_max, max_out, out, mx);
-}
-
-template <int VPL, bool LDS, int MODE>
-const void* fast_kernel_fn(int nf, bool cols = false, int slots_per_lane = 0) {
-    if (cols)
-        return slots_per_lane <= 16 ? reinterpret_cast<const void*>(&k_query_cols<VPL, LDS, MODE, 16>)
-                                    : reinterpret_cast<const void*>(&k_query_cols<VPL, LDS, MODE, 40>);
-    return nf * kFastObs <= kFastPtrsSmall ? reinterpret_cast<const void*>(&k_query_fast<VPL, LDS, MODE, kFastPtrsSmall>)
-                                           : reinterpret_cast<const void*>(&k_query_fast<VPL, LDS, MODE, kFastPtrs>);
-}
-
-template <int VPL, bool LDS, int MODE>
-void allow_fast_lds(int bytes) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_query_slots<VPL, MODE>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_query_fast<VPL, LDS, MODE, kFastPtrsSmall>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_query_fast<VPL, LDS, MODE, kFastPtrs>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_query_cols<VPL, LDS, MODE, 16>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_query_cols<VPL, LDS, MODE, 40>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-}
-
-// The plan's kernel variant as compile-time constants: f(VPL, LDS) with
-// std::integral_constant arguments, resolved from (p->vpl, p->use_lds) once.
-template <class F>
-auto with_variant(const cbn_plan* p, F&& f) {
-    using V1 = std::integral_constant<int, 1>;
-    using V2 = std::integral_constant<int, 2>;
-    if (p->use_lds) return p->vpl == 2 ? f(V2{}, std::true_type{}) : f(V1{}, std::true_type{});
-    return p->vpl == 2 ? f(V2{}, std::false_type{}) : f(V1{}, std::false_type{});
+    });
 }
 
 // CUs a raw launch leaves free (CBN_RAW_RESERVE_CU, diagnostic A/B knob): room
@@ -3085,7 +3032,7 @@ int raw_reserve_cu() {
 // lane) items, at most #CUs x blocks per CU (one max word each); raw and
 // arg-max launches leave raw_reserve_cu() of those free.
 unsigned query_blocks(const cbn_plan* p, long long Q, int L, bool reserve) {
-    const long long cap = reserve ? std::max(1, p->max_slots - raw_reserve_cu()) : p->max_slots;
+    const long long cap = reserve ? std::max(1, p->sel.max_slots - raw_reserve_cu()) : p->sel.max_slots;
     return (unsigned)std::min((Q * L + kQueryThreads - 1) / kQueryThreads, cap);
 }
 
@@ -3100,13 +3047,10 @@ unsigned query_blocks(const cbn_plan* p, long long Q, int L, bool reserve) {
 template <int MODE>
 int launch_mode(cbn_plan* p, long long Q, const EvPtrs& ev, const unsigned* max_in, int n_max, unsigned* max_out,
                 float* out, hipStream_t s, const FoldJob* fold = nullptr, const ModeOut* mx = nullptr) {
-    if (MODE == kModeMax || MODE == kModeRaw) n_max = p->max_slots;
-    with_variant(p, [&](auto vpl, auto lds) {
-        const int L = p->N / (4 * vpl.value);
-        const unsigned blocks =
-            query_blocks(p, Q, L, MODE == kModeRaw || MODE == kModeArgmax || MODE == kModeMoments || MODE == kModeQuantile);
-        launch_fast_k<vpl.value, lds.value, MODE>(p, blocks, s, ev, Q, L, 0u, max_in, n_max, max_out, out, fold, mx);
-    });
+    if (MODE == kModeMax || MODE == kModeRaw) n_max = p->sel.max_slots;
+    const unsigned blocks = query_blocks(
+        p, Q, p->sel.lanes, MODE == kModeRaw || MODE == kModeArgmax || MODE == kModeMoments || MODE == kModeQuantile);
+    launch_fast_k<MODE>(p, blocks, s, ev, Q, 0u, max_in, n_max, max_out, out, fold, mx);
     HIP_TRY(hipGetLastError());
     return CBN_OK;
 }
@@ -3114,17 +3058,14 @@ int launch_mode(cbn_plan* p, long long Q, const EvPtrs& ev, const unsigned* max_
 // Single-launch path: one round per wave, so Q <= blocks * 16 waves * (64 / L);
 // blocks <= #CUs with one block per CU, so every block is resident at once.
 int launch_fused(cbn_plan* p, long long Q, const EvPtrs& ev, unsigned* max_bits, float* out, hipStream_t s) {
-    const int L = p->N / (4 * p->vpl);
-    const long long per_block = (long long)(kQueryThreads / kWave) * (kWave / L);
+    const long long per_block = (long long)(kQueryThreads / kWave) * (kWave / p->sel.lanes);
     long long blocks = (Q + per_block - 1) / per_block;
     // k_query_slots / k_query_cols: beyond one round per block, every CU's block takes two
     // (fused_capacity allows Q <= 2 rounds of the co-resident grid)
-    if ((p->slots || p->cols) && CBN_SLOTS_FUSED2) blocks = std::min<long long>(blocks, std::min<long long>(num_cu(), kMaxSlots));
+    if (p->sel.fused2) blocks = std::min<long long>(blocks, std::min<long long>(num_cu(), kMaxSlots));
     const unsigned epoch = ++p->fused_epoch;  // 1, 2, ... (0 = never published)
     if (p->fused_epoch == 0xFFFFFFFFu) p->fused_epoch = 0;
-    with_variant(p, [&](auto vpl, auto lds) {
-        launch_fast_k<vpl.value, lds.value, kModeFused>(p, (unsigned)blocks, s, ev, Q, L, epoch, nullptr, 0, max_bits, out);
-    });
+    launch_fast_k<kModeFused>(p, (unsigned)blocks, s, ev, Q, epoch, nullptr, 0, max_bits, out);
     HIP_TRY(hipGetLastError());
     return CBN_OK;
 }
@@ -3135,7 +3076,7 @@ int launch_fast(cbn_plan* p, long long Q, const EvPtrs& ev, unsigned* max_bits, 
     if (WRITE) return launch_mode<kModeWrite>(p, Q, ev, max_bits, 1, nullptr, out, s);
     unsigned* slots = p->d_sync + kMaxWordOff;
     if (const int rc = launch_mode<kModeMax>(p, Q, ev, nullptr, 0, slots, nullptr, s)) return rc;
-    hipLaunchKernelGGL(k_reduce_max, dim3(1), dim3(kWave), 0, s, slots, p->max_slots, max_bits);
+    hipLaunchKernelGGL(k_reduce_max, dim3(1), dim3(kWave), 0, s, slots, p->sel.max_slots, max_bits);
     HIP_TRY(hipGetLastError());
     return CBN_OK;
 }
@@ -3187,18 +3128,20 @@ struct Timed {
         if (const int _rc = (expr)) return _rc; \
     } while (0)
 
-template <int VEC, bool LDS, bool WRITE>
+template <bool WRITE>
 int launch_query(cbn_plan* p, long long Q, const EvPtrs& ev, unsigned* max_bits, float* out, hipStream_t s) {
     if (Q == 0) return CBN_OK;
-    if (p->fast) return launch_fast<WRITE>(p, Q, ev, max_bits, out, s);
+    if (p->sel.fast()) return launch_fast<WRITE>(p, Q, ev, max_bits, out, s);
     // every CU busy once there are >= 64 queries per block; a block walks its
     // contiguous range in LDS-sized chunks of CH queries
-    const long long cap = (long long)num_cu() * p->blocks_per_cu;
+    const long long cap = (long long)num_cu() * p->sel.blocks_per_cu;
     long long blocks = (Q + 63) / 64;
     if (blocks > cap) blocks = cap;
-    hipLaunchKernelGGL((k_query<VEC, LDS, WRITE>), dim3((unsigned)blocks), dim3(kQueryThreads), p->lds_bytes, s,
-                       p->d_fac, p->nf, p->d_slots, p->ns, p->d_image, p->image_floats, ev, Q, p->N, p->RS, p->L, p->CH,
-                       p->d_sync, max_bits, out);
+    with_generic_kernel<WRITE>(p, [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(kQueryThreads), p->sel.lds_bytes, s, p->d_fac, p->nf,
+                           p->d_slots, p->ns, p->d_image, p->image_floats, ev, Q, p->N, p->RS, p->L, p->CH, p->d_sync,
+                           max_bits, out);
+    });
     HIP_TRY(hipGetLastError());
     return CBN_OK;
 }
@@ -3210,83 +3153,29 @@ int dispatch_query(cbn_plan* p, long long Q, const float* const* evidence, int n
         return set_err(CBN_E_ARG, "plan has no device buffers");
     EvPtrs ev;
     CBN_TRY(pack_evidence(p, evidence, n_ev, Q, ev));
-    if (p->vec == 4)
-        return p->use_lds ? launch_query<4, true, WRITE>(p, Q, ev, max_bits, out, s)
-                          : launch_query<4, false, WRITE>(p, Q, ev, max_bits, out, s);
-    return p->use_lds ? launch_query<1, true, WRITE>(p, Q, ev, max_bits, out, s)
-                      : launch_query<1, false, WRITE>(p, Q, ev, max_bits, out, s);
-}
-
-template <int VEC, bool LDS, bool WRITE>
-void allow_lds(size_t bytes) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_query<VEC, LDS, WRITE>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-    if constexpr (VEC == 4) {
-        constexpr int M = WRITE ? kModeWrite : kModeMax;
-        allow_fast_lds<1, LDS, M>((int)bytes);
-        allow_fast_lds<2, LDS, M>((int)bytes);
-        allow_fast_lds<1, LDS, kModeFused>((int)bytes);
-        allow_fast_lds<2, LDS, kModeFused>((int)bytes);
-        allow_fast_lds<1, LDS, kModeRaw>((int)bytes);
-        allow_fast_lds<2, LDS, kModeRaw>((int)bytes);
-        allow_fast_lds<1, LDS, kModeArgmax>((int)bytes);
-        allow_fast_lds<2, LDS, kModeArgmax>((int)bytes);
-        allow_fast_lds<1, LDS, kModeMoments>((int)bytes);
-        allow_fast_lds<2, LDS, kModeMoments>((int)bytes);
-        allow_fast_lds<1, LDS, kModeQuantile>((int)bytes);
-        allow_fast_lds<2, LDS, kModeQuantile>((int)bytes);
-    }
+    return launch_query<WRITE>(p, Q, ev, max_bits, out, s);
 }
 
 // the plan's per-row reductions run in its query kernel (kModeArgmax, kModeMoments, and kModeQuantile
 // for up to CBN_MAX_QUANTILES probabilities per query): every fast-path table plan
-bool reduce_native(const cbn_plan* p) { return p->fast && !p->param && !p->direct; }
+bool reduce_native(const cbn_plan* p) { return p->sel.fast() && !p->param && !p->direct; }
 
-// Rows of a factor's table: the product of its observed parents' cards
-// (clamped, so a sum over the factors cannot overflow).
-long long observed_rows(const cbn_factor_desc& h) {
-    long long rows = 1;
-    for (int p = 0; p < h.n_parents && p < kMaxP; ++p)
-        if (h.parent_ev_slot[p] >= 0 && h.parent_card[p] > 0) rows = std::min(rows * h.parent_card[p], 1LL << 40);
-    return rows;
+// the planner's diagnostic switches, read from the environment (under CBN_DIAG=1)
+TableSwitches table_switches() {
+    TableSwitches sw;
+    if (const char* e = diag_env("CBN_FAST_VPL")) sw.fast_vpl = atoi(e);
+    sw.no_paired = diag_env("CBN_NO_PAIRED");
+    sw.no_prefix = diag_env("CBN_NO_PREFIX");
+    sw.no_lds_split = diag_env("CBN_NO_LDS_SPLIT");
+    sw.no_slots = diag_env("CBN_NO_SLOTS");
+    sw.no_staged = diag_env("CBN_NO_STAGED");
+    sw.no_cols = diag_env("CBN_NO_COLS");
+    sw.no_fused = diag_env("CBN_NO_FUSED");
+    if (const char* e = diag_env("CBN_SLOTS_BPC")) sw.slots_bpc = atoi(e) == 2 ? 2 : 1;
+    return sw;
 }
 
-// The product loops' records of k_query_cols / k_query_slots from the fast
-// path's: per observed parent (evidence slot << 24) | row weight in floats.
-// false (the kernel declines the plan): a slot's card beyond int16, a parent
-// whose card is not its slot's, a weight >= 2^24 or a slot >= 256.
-bool col_records(const std::vector<FastRec>& recs, const std::vector<int>& slot_card, int ns, int RS, bool all_lds,
-                 const unsigned long long (&lds_mask)[2], std::vector<ColRec>& cr) {
-    const int nf = (int)recs.size();
-    bool ok = true;
-    for (int sl = 0; sl < ns; ++sl) ok = ok && slot_card[sl] <= 32767;
-    for (int f = 0; f < nf && ok; ++f)
-        for (int q = 0; q < recs[f].n_obs; ++q)
-            ok = ok && (recs[f].card[q] & (kDenseBit - 1)) == slot_card[recs[f].slot[q]];
-    cr.resize(nf);
-    for (int f = 0; f < nf && ok; ++f) {
-        ColRec& c = cr[f];
-        memset(&c, 0, sizeof(c));
-        c.base = recs[f].table_off;
-        c.n_obs = recs[f].n_obs;
-        c.lds = all_lds || ((lds_mask[f >> 6] >> (f & 63)) & 1ull) ? 1 : 0;
-        long long w = RS;
-        for (int q = recs[f].n_obs - 1; q >= 0; --q) {
-            ok = ok && w < (1LL << 24) && recs[f].slot[q] < 256;
-            c.par[q] = (recs[f].slot[q] << 24) | (int)(w & 0xFFFFFF);
-            w *= recs[f].card[q] & (kDenseBit - 1);
-        }
-    }
-    return ok;
-}
-
-long long fused_capacity(const cbn_plan* p) {
-    if (!p->fast || !p->fused_ok) return 0;
-    const int L = p->N / (4 * p->vpl);
-    const long long blocks = std::min(num_cu(), kMaxSlots);  // one block per CU, one barrier slot each
-    // k_query_slots and k_query_cols hold two rounds of products per lane across the barrier
-    return blocks * (kQueryThreads / kWave) * (kWave / L) * ((p->slots || p->cols) && CBN_SLOTS_FUSED2 ? 2 : 1);
-}
+long long plan_fused_capacity(const cbn_plan* p) { return p->fused_ok ? fused_capacity(p->sel, num_cu()) : 0; }
 
 // One per-row reduction of a plan's marginals (cbn_plan_run_argmax / _moments /
 // _quantile; `name`, for messages): the checks they share, then the raw rows by
@@ -3314,7 +3203,7 @@ int run_reduce(cbn_plan* plan, int64_t n_queries, const float* const* evidence, 
             return set_err(CBN_E_ARG, "plan has no device buffers");
     }
     CBN_TRY(take_pending_timeout(plan));
-    if (!table || (fast_raw && plan->fast && !native)) {
+    if (!table || (fast_raw && plan->sel.fast() && !native)) {
         // (the raw launch's per-block maxima go into the plan's own words, unused here)
         CBN_TRY(cbn_plan_run(plan, n_queries, evidence, n_evidence, plan->d_sync + kMaxWordOff, rows,
                              (flags & CBN_RUN_BUILD_TABLES) | CBN_RUN_RAW, stream));
@@ -3425,256 +3314,52 @@ int cbn_plan_create(const cbn_factor_desc* factors, int32_t n_factors, int32_t n
     if (!plan || !factors || n_factors <= 0 || n_samples <= 0)
         return set_err(CBN_E_ARG, "cbn_plan_create: bad arguments");
     *plan = nullptr;
-    const int N = n_samples;
-    const int vec = (N % 4 == 0) ? 4 : 1;
-    const int L = N / vec;
-    if (L > kQueryThreads) return set_err(CBN_E_LIMIT, "N_max %d too large for one block row", N);
-    // Table rows: in LDS, +16 B per row so consecutive rows start 4 banks apart;
-    // an image that cannot fit LDS is read from L2/HBM, where the pad would make
-    // every row straddle one more cache line: unpadded rows, 128-B aligned tables.
-    long long total_rows = 0;
-    for (int f = 0; f < n_factors; ++f) total_rows += observed_rows(factors[f]);
-    const bool global_tables = vec == 4 && total_rows * (N + 4) * 4 > (long long)kLdsBudget;
-    // Paired layout (N = 32, tables in LDS, 8 columns per lane): factor f's rows
-    // sit in bank half (f & 1) of 256-B super-rows -- even factors in banks 0-31,
-    // odd factors in banks 32-63, each class packed from super-row 0.  The fast
-    // kernel then reads the two factors of a pair (and the two halves of a row)
-    // in an order that gives the four queries of every ds_read_b128 lane group
-    // four disjoint 16-bank quarters: conflict-free row gathers (the padded
-    // layout's random rows collide ~2x, profiles/r02_lds_pmc.txt).
-    long long class_rows[2] = {0, 0};
-    int want_vpl = 2;
-    if (const char* e = diag_env("CBN_FAST_VPL")) want_vpl = atoi(e);
-    for (int f = 0; f < n_factors; ++f) class_rows[f & 1] += observed_rows(factors[f]);
-    bool paired = vec == 4 && N == 32 && !global_tables && want_vpl >= 2 && !diag_env("CBN_NO_PAIRED") &&
-                  std::max(class_rows[0], class_rows[1]) * 64 * 4 <= (long long)kLdsBudget * 3 / 4;
-    // leading 1-row factors (roots / unobserved-parent factors) fold into the
-    // first multi-row factor (k_merge_prefix); the staged kernel skips them
-    int prefix = 0;
-    if (paired && !diag_env("CBN_NO_PREFIX")) {
-        while (prefix < n_factors - 1 && prefix < 8 && observed_rows(factors[prefix]) == 1) ++prefix;
-    }
-    const int RS = paired ? 64 : vec == 4 && !global_tables ? N + 4 : N;
-    const long long talign = global_tables ? 32 : 4;
-    // Global-table plans: the smallest tables go first in the image, as many as
-    // fit the LDS the fast kernel leaves free (without costing it its second
-    // block per CU), and k_query_fast copies that prefix into LDS -- an
-    // ALARM-like plan is 24 tables of <= 2 KB beside two of 128 KB, and
-    // gathering the small ones from L2 cost as much as the large ones.
-    std::vector<long long> pre_off(n_factors, -1);
-    long long lds_tab_end = 0;
-    unsigned long long lds_mask[2] = {0, 0};
-    if (global_tables && vec == 4 && n_factors <= 128 && !diag_env("CBN_NO_LDS_SPLIT")) {
-        int vp = 0, Lp = 0;
-        for (int c : {2, 1}) {  // the fast path's choice (below)
-            if (c > want_vpl || (N / 4) % c) continue;
-            const int Lc = N / (4 * c);
-            if (Lc <= kWave && (kWave % Lc) == 0) { vp = c; Lp = Lc; break; }
-        }
-        if (vp > 0) {
-            const long long nf4 = (n_factors + 3) & ~3;
-            long long side = (long long)kFastPtrs * sizeof(void*) +
-                             (long long)(kQueryThreads / kWave) * (kWave / Lp) * nf4 * 4 + (kQueryThreads / kWave) * 4 + 64;
-            long long recb = (long long)n_factors * kRecFloats * 4;  // the records go to LDS too
-            if (Lp > 2 && !diag_env("CBN_NO_SLOTS")) {
-                // k_query_slots (>= 4 lanes per query) takes the plan if it can:
-                // budget the small tables beside ITS side buffers -- or beside
-                // k_query_fast's side + records where those are larger, since
-                // the fast gate (below) runs first and k_query_slots may still
-                // decline the plan (a card > 32767, a row weight >= 2^24)
-                int ns_est = 0;
-                for (int f = 0; f < n_factors; ++f)
-                    for (int q = 0; q < factors[f].n_parents && q < kMaxP; ++q)
-                        ns_est = std::max(ns_est, factors[f].parent_ev_slot[q] + 1);
-                side = std::max((long long)slots_lds_bytes(0, ns_est, n_factors, kQueryThreads / Lp), side + recb);
-                recb = 0;
-            }
-            long long budget = (long long)kLdsBudget - side - recb - 1024;  // bytes
-            if (2 * (side + recb) <= (long long)kLdsBudget)
-                budget = std::min(budget, (long long)kLdsBudget / 2 - side - recb - 1024);
-            std::vector<std::pair<long long, int>> by_size;
-            for (int f = 0; f < n_factors; ++f)
-                by_size.push_back({(observed_rows(factors[f]) * RS + talign - 1) & ~(talign - 1), f});
-            std::stable_sort(by_size.begin(), by_size.end());
-            for (const auto& [tf, f] : by_size) {
-                if ((lds_tab_end + tf) * 4 > budget) break;  // floats vs bytes
-                pre_off[f] = lds_tab_end;
-                lds_tab_end += tf;
-                lds_mask[f >> 6] |= 1ull << (f & 63);
-            }
-            if (lds_tab_end == 0 || lds_tab_end * 4 > (1LL << 20)) {
-                std::fill(pre_off.begin(), pre_off.end(), -1);
-                lds_tab_end = 0;
-                lds_mask[0] = lds_mask[1] = 0;
-            }
-        }
-    }
-    long long class_start[2] = {0, 0};
-    std::vector<DevFactor> fac(n_factors);
-    std::vector<const float*> slot_dom(CBN_MAX_EVIDENCE, nullptr);
-    std::vector<int> slot_card(CBN_MAX_EVIDENCE, 0);
-    int ns = 0;
-    long long off = lds_tab_end;  // after the LDS-copied small tables (global-table plans)
-    for (int f = 0; f < n_factors; ++f) {
-        const cbn_factor_desc& h = factors[f];
-        DevFactor& d = fac[f];
-        memset(&d, 0, sizeof(d));
-        if (h.kind < CBN_FACTOR_SCALAR || h.kind > CBN_FACTOR_QUERY)
-            return set_err(CBN_E_ARG, "factor %d: bad kind %d", f, h.kind);
-        if (h.n_parents < 0 || h.n_parents > kMaxP)
-            return set_err(CBN_E_LIMIT, "factor %d: %d parents > %d", f, h.n_parents, kMaxP);
-        if ((h.kind == CBN_FACTOR_SCALAR) != (h.n_parents == 0))
-            return set_err(CBN_E_ARG, "factor %d: SCALAR iff root", f);
-        if (!h.cpd || !h.node_sample_idx || h.node_card <= 0)
-            return set_err(CBN_E_ARG, "factor %d: missing cpd/node samples", f);
-        d.kind = h.kind;
-        d.n_parents = h.n_parents;
-        d.node_card = h.node_card;
-        d.cpd = h.cpd;
-        d.node_sample_idx = h.node_sample_idx;
-        d.parent_sample_idx = h.parent_sample_idx;
-        long long stride = h.node_card, rows = 1, F = 1;
-        for (int p = h.n_parents - 1; p >= 0; --p) {
-            if (h.parent_card[p] <= 0) return set_err(CBN_E_ARG, "factor %d: parent %d card", f, p);
-            d.parent_card[p] = h.parent_card[p];
-            d.ev_slot[p] = h.parent_ev_slot[p];
-            d.cpd_stride[p] = (int)stride;
-            stride *= h.parent_card[p];
-            if (stride >= (1LL << 31)) return set_err(CBN_E_LIMIT, "factor %d: CPD too large", f);
-            const int sl = h.parent_ev_slot[p];
-            if (sl >= 0) {
-                if (sl >= CBN_MAX_EVIDENCE || !h.parent_domain[p])
-                    return set_err(CBN_E_ARG, "factor %d: bad evidence slot/domain", f);
-                if (!slot_dom[sl]) {
-                    slot_dom[sl] = h.parent_domain[p];
-                    slot_card[sl] = h.parent_card[p];
-                } else if (slot_card[sl] != h.parent_card[p]) {
-                    return set_err(CBN_E_ARG, "evidence slot %d used with different domains", sl);
-                }
-                ns = std::max(ns, sl + 1);
-                rows *= h.parent_card[p];
-            } else {
-                if (!h.parent_sample_idx) return set_err(CBN_E_ARG, "factor %d: free parent without samples", f);
-                F *= N;
-                if (F >= (1LL << 31)) return set_err(CBN_E_LIMIT, "factor %d: too many free combos", f);
-                d.n_free++;
-            }
-        }
-        if ((h.kind == CBN_FACTOR_QUERY) != (rows > 1 || d.n_parents - d.n_free > 0))
-            return set_err(CBN_E_ARG, "factor %d: QUERY iff some parent observed", f);
-        if (rows * (long long)RS >= (1LL << 30)) return set_err(CBN_E_LIMIT, "factor %d: table too large", f);
-        d.rows = (int)rows;
-        d.free_combos = (int)F;
-        d.n_entries = (int)(rows * N);
-        const long long F_eff = h.kind == CBN_FACTOR_SCALAR ? N : F;
-        d.wave_mode = F_eff >= kWave ? 1 : 0;
-        if (paired) {
-            // bank half by the index the staged kernel sees (prefix factors: half 0, never read there)
-            const int c = f < prefix ? 0 : (f - prefix) & 1;
-            d.table_off = (int)(class_start[c] * 64 + c * 32);
-            class_start[c] += rows;
-            off = std::max(class_start[0], class_start[1]) * 64;
-        } else if (pre_off[f] >= 0) {
-            if (pre_off[f] + rows * RS > lds_tab_end) return set_err(CBN_E_ARG, "factor %d: table size changed", f);
-            d.table_off = (int)pre_off[f];
-        } else {
-            d.table_off = (int)off;
-            off += (rows * RS + talign - 1) & ~(talign - 1);
-        }
-    }
-    for (int sl = 0; sl < ns; ++sl)
-        if (!slot_dom[sl]) return set_err(CBN_E_ARG, "evidence slot %d is not used by any factor", sl);
-    // paired layout: a zero super-row (values outside a domain) and a ones
-    // super-row (padding slots) after the tables, both bank halves each
-    const long long zero_off = paired ? off : -1;
-    if (paired) off += 128;
-    const long long table_floats = off;
-    std::vector<QSlot> qs(ns);
-    std::vector<float> hdom;
-    for (int sl = 0; sl < ns; ++sl) {
-        qs[sl].dom_off = (int)off;
-        qs[sl].card = slot_card[sl];
-        hdom.resize(slot_card[sl]);
-        if (hipMemcpy(hdom.data(), slot_dom[sl], sizeof(float) * slot_card[sl], hipMemcpyDeviceToHost) != hipSuccess)
-            return set_err(CBN_E_HIP, "cbn_plan_create: domain read failed");
-        int dense = 1;
-        for (int i = 0; i < slot_card[sl] && dense; ++i) dense = hdom[i] == (float)i;
-        qs[sl].dense = dense;
-        off += (slot_card[sl] + 3) & ~3LL;
-    }
-    const long long rec_off = off;  // FastRec array (fast path), copied to LDS with the tables
-    off += (long long)n_factors * kRecFloats;
-    off += (long long)ns * 4;  // QSlot array right after it (k_query_cols: one LDS-DMA for both)
-    if (off >= (1LL << 30)) return set_err(CBN_E_LIMIT, "plan image too large");
+    // layout, LDS sizes and the kernel: decided on the host from the descriptors' integers
+    TablePlan t = plan_table(factors, n_factors, n_samples, num_cu(), table_switches());
+    if (t.err) return set_err(t.err, "%s", t.msg);
+    const int ns = t.ns;
+    const size_t image_floats = (size_t)std::max(t.image_floats, 4);
 
     cbn_plan* P = new cbn_plan();
-    P->nf = n_factors;
-    P->ns = ns;
-    P->N = N;
-    P->vec = vec;
-    P->L = L;
-    P->image_floats = (int)off;
-    P->table_floats = (int)table_floats;
-    P->zero_off = (int)zero_off;
-    P->prefix = prefix;
-    for (int i = 0; i <= prefix && i < 9; ++i) P->prefix_offs[i] = fac[i].table_off;
-    P->prefix_rows = prefix > 0 ? fac[prefix].rows : 0;
-    P->rec_off = (int)rec_off;
-    P->RS = RS;
-    P->lds_tab_floats = (int)lds_tab_end;
-    P->lds_tab_mask[0] = lds_mask[0];
-    P->lds_tab_mask[1] = lds_mask[1];
-    // LDS: [image (if staged)] [factor records] [slots] [CH x (ns + nf) ints] [wave maxima]
-    const size_t fixed = (size_t)n_factors * kFqInts * 4 + (size_t)ns * sizeof(QSlot) + (kQueryThreads / kWave) * 4 +
-                         (size_t)CBN_MAX_EVIDENCE * sizeof(void*) + 64;
-    const size_t per_q = (size_t)(ns + n_factors) * 4;
-    const size_t img_bytes = (size_t)off * 4;
-    auto chunk_for = [&](size_t avail) -> int {
-        if (avail <= fixed) return 0;
-        size_t ch = (avail - fixed) / per_q;
-        return (int)std::min<size_t>(ch, 1024);
+    static_cast<TableLayout&>(*P) = t;
+    auto fail = [&](const char* what) {
+        cbn_plan_destroy(P);
+        return set_err(CBN_E_HIP, "cbn_plan_create: %s", what);
     };
-    int ch = global_tables ? 0 : chunk_for(kLdsBudget > img_bytes ? kLdsBudget - img_bytes : 0);
-    P->use_lds = ch >= 64;  // (a global-table layout stays in L2/HBM even if the unpadded image would fit)
-    if (!P->use_lds) ch = chunk_for(kLdsBudget);
-    if (ch < 1) {
-        delete P;
-        return set_err(CBN_E_LIMIT, "plan needs more LDS than a CU has (nf=%d, ns=%d)", n_factors, ns);
-    }
-    P->CH = ch;
-    P->lds_bytes = ((P->use_lds ? img_bytes : 0) + fixed + (size_t)ch * per_q + 15) & ~size_t(15);
-    P->blocks_per_cu = 2 * P->lds_bytes <= (size_t)kLdsBudget ? 2 : 1;
+    auto upload = [](void* dst, const void* src, size_t bytes) {
+        return bytes == 0 || hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice) == hipSuccess;
+    };
 
-    std::vector<BuildItem> build;
-    int units = 0;
-    for (int f = 0; f < n_factors; ++f) {
-        const DevFactor& d = fac[f];
-        const int nu = d.wave_mode ? d.n_entries : (d.n_entries + kWave - 1) / kWave;
-        build.push_back({f, units});
-        units += nu;
+    // the slots' dense bit (domain = {0 .. card-1}: index = value) is the one
+    // fact that needs the device; no decision depends on it
+    std::vector<float> hdom;
+    for (int sl = 0; sl < ns; ++sl) {
+        QSlot& q = t.slots[sl];
+        hdom.resize(q.card);
+        if (hipMemcpy(hdom.data(), t.slot_dom[sl], sizeof(float) * q.card, hipMemcpyDeviceToHost) != hipSuccess)
+            return fail("domain read failed");
+        q.dense = 1;
+        for (int i = 0; i < q.card && q.dense; ++i) q.dense = hdom[i] == (float)i;
     }
-    P->n_build = (int)build.size();
-    P->build_units = units;
+    for (FastRec& r : t.recs)
+        for (int q = 0; q < r.n_obs; ++q) r.card[q] |= t.slots[r.slot[q]].dense ? kDenseBit : 0;
 
-    bool ok = hipMalloc(&P->d_fac, sizeof(DevFactor) * n_factors) == hipSuccess &&
+    bool ok = hipMalloc(&P->d_fac, sizeof(DevFactor) * t.nf) == hipSuccess &&
               hipMalloc(&P->d_slots, sizeof(QSlot) * std::max(ns, 1)) == hipSuccess &&
-              hipMalloc(&P->d_build, sizeof(BuildItem) * std::max<size_t>(build.size(), 1)) == hipSuccess &&
-              hipMalloc(&P->d_image, sizeof(float) * std::max<long long>(off, 4)) == hipSuccess &&
+              hipMalloc(&P->d_build, sizeof(BuildItem) * t.build.size()) == hipSuccess &&
+              hipMalloc(&P->d_image, sizeof(float) * image_floats) == hipSuccess &&
               hipMalloc(&P->d_sync, sizeof(unsigned) * kSyncWords) == hipSuccess;
-    ok = ok && hipMemcpy(P->d_fac, fac.data(), sizeof(DevFactor) * n_factors, hipMemcpyHostToDevice) == hipSuccess;
-    ok = ok && (ns == 0 || hipMemcpy(P->d_slots, qs.data(), sizeof(QSlot) * ns, hipMemcpyHostToDevice) == hipSuccess);
-    ok = ok && (build.empty() ||
-                hipMemcpy(P->d_build, build.data(), sizeof(BuildItem) * build.size(), hipMemcpyHostToDevice) == hipSuccess);
-    ok = ok && hipMemset(P->d_image, 0, sizeof(float) * std::max<long long>(off, 4)) == hipSuccess;
-    if (ok && paired) {
+    ok = ok && upload(P->d_fac, t.fac.data(), sizeof(DevFactor) * t.nf);
+    ok = ok && upload(P->d_slots, t.slots.data(), sizeof(QSlot) * ns);
+    ok = ok && upload(P->d_build, t.build.data(), sizeof(BuildItem) * t.build.size());
+    ok = ok && hipMemset(P->d_image, 0, sizeof(float) * image_floats) == hipSuccess;
+    if (ok && t.paired_layout) {
         const std::vector<float> ones(64, 1.f);
-        ok = hipMemcpy(P->d_image + zero_off + 64, ones.data(), sizeof(float) * 64, hipMemcpyHostToDevice) == hipSuccess;
+        ok = upload(P->d_image + t.zero_off + 64, ones.data(), sizeof(float) * 64);
     }
     ok = ok && hipMemset(P->d_sync, 0, sizeof(unsigned) * kSyncWords) == hipSuccess;
-    if (ok) {  // the bits of 1.0f: the max word of cbn_plan_run_argmax's generic-plan rows (x / 1.0f = x)
-        const float one = 1.f;
-        ok = hipMemcpy(P->d_sync + kOneWordOff, &one, sizeof(one), hipMemcpyHostToDevice) == hipSuccess;
-    }
+    const float one = 1.f;  // its bits: the max word of cbn_plan_run_argmax's generic-plan rows (x / 1.0f = x)
+    ok = ok && upload(P->d_sync + kOneWordOff, &one, sizeof(one));
     // host-mapped status word of the fused launches' timeout (polled for free by cbn_plan_run);
     // its device address lives in the sync buffer for the (rare) timeout path
     ok = ok && hipHostMalloc(reinterpret_cast<void**>(&P->h_status), sizeof(unsigned),
@@ -3683,178 +3368,62 @@ int cbn_plan_create(const cbn_factor_desc* factors, int32_t n_factors, int32_t n
         *P->h_status = 0;
         unsigned* dh = nullptr;
         ok = hipHostGetDevicePointer(reinterpret_cast<void**>(&dh), P->h_status, 0) == hipSuccess &&
-             hipMemcpy(P->d_sync + kHostStatusWordOff, &dh, sizeof(dh), hipMemcpyHostToDevice) == hipSuccess;
+             upload(P->d_sync + kHostStatusWordOff, &dh, sizeof(dh));
     }
     for (int sl = 0; ok && sl < ns; ++sl)
-        ok = hipMemcpy(P->d_image + qs[sl].dom_off, slot_dom[sl], sizeof(float) * slot_card[sl],
+        ok = hipMemcpy(P->d_image + t.slots[sl].dom_off, t.slot_dom[sl], sizeof(float) * t.slots[sl].card,
                        hipMemcpyDeviceToDevice) == hipSuccess;
     ok = ok && hipDeviceSynchronize() == hipSuccess;  // uploads complete before any launch uses them
-    if (!ok) {
-        cbn_plan_destroy(P);
-        return set_err(CBN_E_HIP, "cbn_plan_create: device allocation/upload failed");
-    }
+    if (!ok) return fail("device allocation/upload failed");
 
-    // fast path eligibility: N % 4 == 0, lanes per query L = N / (4 VPL) a power
-    // of two <= 64, <= kLoc factors per lane, <= kFastObs observed parents each
-    bool fast = vec == 4 && n_factors * kFastObs <= kFastPtrs;
-    std::vector<FastRec> recs(n_factors);
-    for (int& sl : P->fast_slot) sl = -1;
-    for (int f = 0; f < n_factors && fast; ++f) {
-        FastRec& r = recs[f];
-        memset(&r, 0, sizeof(r));
-        r.table_off = fac[f].table_off;
-        for (int p = 0; p < fac[f].n_parents; ++p) {
-            const int sl = fac[f].ev_slot[p];
-            if (sl >= 0) {
-                if (r.n_obs == kFastObs) { fast = false; break; }
-                r.card[r.n_obs] = fac[f].parent_card[p] | (qs[sl].dense ? kDenseBit : 0);
-                r.dom_off[r.n_obs] = qs[sl].dom_off;
-                r.slot[r.n_obs] = sl;
-                P->fast_slot[f * kFastObs + r.n_obs] = sl;
-                ++r.n_obs;
-            }
-        }
-    }
-    int vpl = 0, Lf = 0;
-    if (fast) {
-        int want = 2;  // 8 output values per lane (tuned on MI355X: chain20 d32)
-        if (const char* e = diag_env("CBN_FAST_VPL")) want = atoi(e);
-        for (int c : {2, 1}) {  // VPL 4 exceeds 128 VGPRs at 1024 threads (spills)
-            if (c > want || (N / 4) % c) continue;
-            const int Lc = N / (4 * c);
-            if (Lc <= kWave && (kWave % Lc) == 0) { vpl = c; Lf = Lc; break; }
-        }
-        fast = vpl > 0;
-    }
-    if (fast) {
-        const int nf4 = (n_factors + 3) & ~3;
-        const size_t side = (size_t)kFastPtrs * sizeof(void*) +
-                            (size_t)(kQueryThreads / kWave) * (kWave / Lf) * nf4 * 4 + (kQueryThreads / kWave) * 4 + 64;
-        const bool lds_ok = img_bytes + side <= (size_t)kLdsBudget;
-        if (!lds_ok && P->use_lds) fast = false;  // keep one LDS mode per plan
-        // global tables: the LDS-copied small tables + the records + the side buffers must fit
-        if (!P->use_lds && (size_t)P->lds_tab_floats * 4 + (size_t)n_factors * kRecFloats * 4 + side > (size_t)kLdsBudget)
-            fast = false;
-        if (fast) {
-            P->fast = true;
-            P->vpl = vpl;
-            P->paired = paired && vpl == 2 && P->use_lds;
-            const int st_T = (n_factors - P->prefix + 2) >> 1, st_S = (st_T + 1) >> 1;  // k_query_staged's nsl
-            const size_t st_bytes =
-                img_bytes + (size_t)2 * kSR * (4 * (st_S + 1)) * 4 + (kQueryThreads / kWave) * 4 + 64;
-            if (P->paired && (n_factors - P->prefix) * kFastObs <= kFastPtrsSmall && st_bytes <= (size_t)kLdsBudget &&
-                !diag_env("CBN_NO_STAGED")) {
-                P->staged = true;
-                P->staged_lds_bytes = (st_bytes + 15) & ~size_t(15);
-                for (const void* fn : {reinterpret_cast<const void*>(&k_query_staged<kModeMax>),
-                                       reinterpret_cast<const void*>(&k_query_staged<kModeWrite>),
-                                       reinterpret_cast<const void*>(&k_query_staged<kModeFused>),
-                                       reinterpret_cast<const void*>(&k_query_staged<kModeRaw>),
-                                       reinterpret_cast<const void*>(&k_query_staged<kModeArgmax>),
-                                       reinterpret_cast<const void*>(&k_query_staged<kModeMoments>),
-                                       reinterpret_cast<const void*>(&k_query_staged<kModeQuantile>)})
-                    (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBudget);
-            }
-            P->fast_lds_bytes =
-                ((P->use_lds ? img_bytes : (size_t)P->lds_tab_floats * 4 + (size_t)n_factors * kRecFloats * 4) + side +
-                 15) & ~size_t(15);
-            // column-staged kernel (k_query_cols): non-paired plans of <= 2
-            // lanes per query (N <= 16) whose slot indices fit int16 and whose
-            // per-slot index buffer fits LDS.  With more lanes per query every
-            // lane re-forms every factor's offset: the configs[4] grid (L = 8)
-            // ran 459 -> 534 us at 262 144 queries (profiles/r04_cols_ab.json)
-            if (!P->staged && !P->paired && Lf <= 2 && ns <= kFastPtrsSmall && n_factors <= kWave &&
-                !diag_env("CBN_NO_COLS")) {
-                std::vector<ColRec> cr;
-                bool ok_c = col_records(recs, slot_card, ns, RS, P->use_lds, lds_mask, cr);
-                const size_t QBc = (size_t)kQueryThreads / Lf;
-                const size_t cols_bytes =
-                    ((P->use_lds ? img_bytes
-                                 : (size_t)P->lds_tab_floats * 4 + ((size_t)n_factors * kRecFloats + (size_t)ns * 4) * 4) +
-                     (size_t)((ns + 1) & ~1) * sizeof(void*) + (((size_t)ns * QBc + 1) & ~size_t(1)) * 2 +
-                     (kQueryThreads / kWave) * 4 + 64 + 16 + (size_t)N * 4 + 15) & ~size_t(15);  // (+ zero row)
-                if (ok_c && cols_bytes <= (size_t)kLdsBudget) {
-                    ok_c = hipMalloc(&P->d_crec, sizeof(ColRec) * n_factors) == hipSuccess &&
-                           hipMemcpy(P->d_crec, cr.data(), sizeof(ColRec) * n_factors, hipMemcpyHostToDevice) ==
-                               hipSuccess;
-                    if (!ok_c) {
-                        cbn_plan_destroy(P);
-                        return set_err(CBN_E_HIP, "cbn_plan_create: column records upload failed");
-                    }
-                    P->cols = true;
-                    P->fast_lds_bytes = cols_bytes;
-                }
-            }
-            // slot-indexed kernel (k_query_slots, round 5): global-table plans of
-            // >= 4 lanes per query (the configs[4] grid) -- the slots' evidence
-            // loaded once per query instead of kFastObs loads per factor
-            if (!P->staged && !P->paired && !P->cols && !P->use_lds && Lf > 2 && ns <= kFastPtrsSmall &&
-                n_factors <= 128 && !diag_env("CBN_NO_SLOTS")) {
-                std::vector<ColRec> cr;
-                bool ok_s = col_records(recs, slot_card, ns, RS, false, lds_mask, cr);
-                // the offset (table base + row x RS) must fit an int
-                for (int f = 0; f < n_factors; ++f)
-                    ok_s = ok_s && (long long)recs[f].table_off + (long long)fac[f].rows * RS < (1LL << 31);
-                const size_t sb = slots_lds_bytes(P->lds_tab_floats, ns, n_factors, kQueryThreads / Lf);
-                if (ok_s && sb <= (size_t)kLdsBudget) {
-                    if (hipMalloc(&P->d_crec, sizeof(ColRec) * n_factors) != hipSuccess ||
-                        hipMemcpy(P->d_crec, cr.data(), sizeof(ColRec) * n_factors, hipMemcpyHostToDevice) !=
-                            hipSuccess) {
-                        cbn_plan_destroy(P);
-                        return set_err(CBN_E_HIP, "cbn_plan_create: slot records upload failed");
-                    }
-                    P->slots = true;
-                    P->fast_lds_bytes = sb;
-                }
-            }
-            P->fast_blocks_per_cu = 2 * P->fast_lds_bytes <= (size_t)kLdsBudget ? 2 : 1;
-            if (P->slots)
-                if (const char* e = diag_env("CBN_SLOTS_BPC")) P->fast_blocks_per_cu = atoi(e) == 2 ? 2 : 1;
-            P->max_slots = std::min(num_cu() * P->fast_blocks_per_cu, kMaxSlots);
-            if (hipMemcpy(P->d_image + rec_off, recs.data(), sizeof(FastRec) * n_factors, hipMemcpyHostToDevice) !=
-                    hipSuccess ||
-                (ns > 0 && hipMemcpy(P->d_image + rec_off + (long long)n_factors * kRecFloats, qs.data(),
-                                     sizeof(QSlot) * ns, hipMemcpyHostToDevice) != hipSuccess)) {
-                cbn_plan_destroy(P);
-                return set_err(CBN_E_HIP, "cbn_plan_create: fast records upload failed");
-            }
-            if (!diag_env("CBN_NO_FUSED")) {
-                // the grid barrier needs every block resident: check one block per CU fits
-                // (tables in LDS, or -- image beyond LDS -- read from L2/HBM)
-                allow_fast_lds<1, true, kModeFused>(kLdsBudget);
-                allow_fast_lds<2, true, kModeFused>(kLdsBudget);
-                allow_fast_lds<1, false, kModeFused>(kLdsBudget);
-                allow_fast_lds<2, false, kModeFused>(kLdsBudget);
-                int nb = 0;
-                const int spl = (ns + Lf - 1) / Lf;  // k_query_cols: slots per lane
-                const void* fn = with_variant(P, [&](auto v, auto lds) {
-                    if (P->staged) return reinterpret_cast<const void*>(&k_query_staged<kModeFused>);
-                    if (P->slots) return reinterpret_cast<const void*>(&k_query_slots<v.value, kModeFused>);
-                    return fast_kernel_fn<v.value, lds.value, kModeFused>(n_factors, P->cols, spl);
-                });
-                const size_t lb = P->staged ? P->staged_lds_bytes : P->fast_lds_bytes;
-                if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, kQueryThreads, lb) == hipSuccess && nb >= 1)
-                    P->fused_ok = true;
-            }
-        }
-    }
-    if (!P->staged && P->prefix) {
-        // the merge is only valid for the staged kernel (the others multiply every
-        // factor): a non-staged plan with a paired layout keeps its tables as built
-        P->prefix = 0;
-        P->prefix_rows = 0;
-    }
-    allow_lds<4, true, false>(kLdsBudget); allow_lds<4, true, true>(kLdsBudget);
-    allow_lds<1, true, false>(kLdsBudget); allow_lds<1, true, true>(kLdsBudget);
-    allow_lds<4, false, false>(kLdsBudget); allow_lds<4, false, true>(kLdsBudget);
-    allow_lds<1, false, false>(kLdsBudget); allow_lds<1, false, true>(kLdsBudget);
-    // invariant: every buffer a launch dereferences exists (a plan missing one
-    // must never reach a kernel)
-    if (!P->d_fac || !P->d_slots || !P->d_build || !P->d_image || !P->d_sync) {
-        cbn_plan_destroy(P);
-        return set_err(CBN_E_HIP, "cbn_plan_create: internal error, plan buffer missing");
+    const bool crec = P->sel.kernel == TableKernel::Cols || P->sel.kernel == TableKernel::Slots;
+    if (crec && (hipMalloc(&P->d_crec, sizeof(ColRec) * t.nf) != hipSuccess ||
+                 !upload(P->d_crec, t.crec.data(), sizeof(ColRec) * t.nf)))
+        return fail(P->sel.kernel == TableKernel::Cols ? "column records upload failed" : "slot records upload failed");
+    // fast path: the records, then the QSlots, in the image
+    if (P->sel.fast() && !(upload(P->d_image + t.rec_off, t.recs.data(), sizeof(FastRec) * t.nf) &&
+                           upload(P->d_image + t.rec_off + (long long)t.nf * kRecFloats, t.slots.data(),
+                                  sizeof(QSlot) * ns)))
+        return fail("fast records upload failed");
+    if (P->sel.kernel == TableKernel::Slots && slots_sidx_stride(P->sel.lanes) != slots_sidx_stride_host(P->sel.lanes))
+        return fail("internal error, k_query_slots' LDS layout and its host size disagree");
+
+    allow_plan_lds(P, AllModes{});
+    if (t.fused_candidate) {
+        // the grid barrier needs every block resident: check one block per CU fits
+        // (tables in LDS, or -- image beyond LDS -- read from L2/HBM)
+        int nb = 0;
+        const void* fn = with_kernel<kModeFused>(
+            P->sel, [](auto, auto, auto kernel) { return reinterpret_cast<const void*>(kernel); });
+        P->fused_ok = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, kQueryThreads, P->sel.lds_bytes) ==
+                          hipSuccess && nb >= 1;
     }
     *plan = P;
+    return CBN_OK;
+}
+
+int cbn_table_plan_info(const cbn_factor_desc* factors, int32_t n_factors, int32_t n_samples, int32_t n_cu,
+                        struct cbn_table_plan_info* out) {
+    if (!out || !factors || n_factors <= 0 || n_samples <= 0 || n_cu <= 0)
+        return set_err(CBN_E_ARG, "cbn_table_plan_info: bad arguments");
+    if (out->struct_bytes != (int32_t)sizeof(*out))
+        return set_err(CBN_E_ARG, "cbn_table_plan_info: struct_bytes %d, this library's is %d", out->struct_bytes,
+                       (int)sizeof(*out));
+    const TablePlan t = plan_table(factors, n_factors, n_samples, n_cu, table_switches());
+    if (t.err) return set_err(t.err, "%s", t.msg);
+    out->flags = table_flags(t.sel);
+    out->kernel = (int32_t)t.sel.kernel;
+    out->vpl = t.sel.vpl;
+    out->lanes = t.sel.lanes;
+    out->row_stride = t.RS;
+    out->prefix = t.prefix;
+    out->lds_tab_floats = t.lds_tab_floats;
+    out->lds_bytes = (int32_t)t.sel.lds_bytes;
+    out->blocks_per_cu = t.sel.blocks_per_cu;
+    out->max_slots = t.sel.max_slots;
+    out->fused_candidate = t.fused_candidate ? 1 : 0;
+    out->table_bytes = (int64_t)t.image_floats * 4;
+    out->fused_capacity = t.fused_candidate ? fused_capacity(t.sel, n_cu) : 0;
     return CBN_OK;
 }
 
@@ -3880,7 +3449,7 @@ int64_t cbn_plan_table_bytes(const cbn_plan* plan) {
     return plan ? (int64_t)plan->image_floats * (int64_t)sizeof(float) : -1;
 }
 
-int cbn_plan_uses_lds(const cbn_plan* plan) { return plan && plan->use_lds ? 1 : 0; }
+int cbn_plan_uses_lds(const cbn_plan* plan) { return plan && plan->sel.use_lds ? 1 : 0; }
 
 int cbn_plan_build_tables(cbn_plan* plan, void* stream) {
     if (!plan) return set_err(CBN_E_ARG, "null plan");
@@ -3945,7 +3514,7 @@ int cbn_plan_run(cbn_plan* plan, int64_t n_queries, const float* const* evidence
     unsigned* words = plan->d_sync ? plan->d_sync + kMaxWordOff : nullptr;  // the plan's per-block max words
     EvPtrs ev;
     if (flags & CBN_RUN_RAW) {
-        if (!plan->fast) return set_err(CBN_E_UNSUPPORTED, "cbn_plan_run: raw launch needs a fast-path plan");
+        if (!plan->sel.fast()) return set_err(CBN_E_UNSUPPORTED, "cbn_plan_run: raw launch needs a fast-path plan");
         CBN_TRY(pack_evidence(plan, evidence, n_evidence, n_queries, ev));
         if (!out || !max_bits) return set_err(CBN_E_ARG, "cbn_plan_run: null output");
         if (!plan->d_image || !plan->d_sync) return set_err(CBN_E_ARG, "plan has no device buffers");
@@ -3954,7 +3523,7 @@ int cbn_plan_run(cbn_plan* plan, int64_t n_queries, const float* const* evidence
         CBN_TRY(launch_mode<kModeRaw>(plan, n_queries, ev, nullptr, 0, max_bits, out, s));
         return t.mark(2);
     }
-    if (one_pass && fused_capacity(plan) >= n_queries) {
+    if (one_pass && plan_fused_capacity(plan) >= n_queries) {
         // one launch: both passes with the products held in registers across a grid barrier
         CBN_TRY(pack_evidence(plan, evidence, n_evidence, n_queries, ev));
         if (!out || !max_bits) return set_err(CBN_E_ARG, "cbn_plan_run: null output");
@@ -3962,7 +3531,7 @@ int cbn_plan_run(cbn_plan* plan, int64_t n_queries, const float* const* evidence
         CBN_TRY(launch_fused(plan, n_queries, ev, max_bits, out, s));
         return t.mark(2);
     }
-    if (plan->fast && one_pass && reinterpret_cast<uintptr_t>(out) % 16 == 0) {
+    if (plan->sel.fast() && one_pass && reinterpret_cast<uintptr_t>(out) % 16 == 0) {
         // beyond the single launch: ONE compute pass (raw: unnormalised rows +
         // per-block maxima) and an HBM-bound in-place scale that reduces the
         // words, divides and publishes the max in *max_bits -- instead of
@@ -3971,17 +3540,17 @@ int cbn_plan_run(cbn_plan* plan, int64_t n_queries, const float* const* evidence
         if (!max_bits) return set_err(CBN_E_ARG, "cbn_plan_run: null output");
         CBN_TRY(launch_mode<kModeRaw>(plan, n_queries, ev, nullptr, 0, words, out, s));
         CBN_TRY(t.mark(1));
-        CBN_TRY(launch_scale(out, n_queries * (long long)plan->N, words, plan->max_slots, max_bits, s));
+        CBN_TRY(launch_scale(out, n_queries * (long long)plan->N, words, plan->sel.max_slots, max_bits, s));
         return t.mark(2);
     }
-    if (plan->fast && n_queries > 0) {
+    if (plan->sel.fast() && n_queries > 0) {
         // two launches: per-block maxima into the plan's words, then the write
         // pass reduces them itself and publishes the max in *max_bits
         CBN_TRY(pack_evidence(plan, evidence, n_evidence, n_queries, ev));
         if (!out || !max_bits) return set_err(CBN_E_ARG, "cbn_plan_run: null output");
         CBN_TRY(launch_mode<kModeMax>(plan, n_queries, ev, nullptr, 0, words, nullptr, s));
         CBN_TRY(t.mark(1));
-        CBN_TRY(launch_mode<kModeWrite>(plan, n_queries, ev, words, plan->max_slots, max_bits, out, s));
+        CBN_TRY(launch_mode<kModeWrite>(plan, n_queries, ev, words, plan->sel.max_slots, max_bits, out, s));
         return t.mark(2);
     }
     // generic plans (and empty batches): the public max and write passes
@@ -3997,7 +3566,7 @@ int cbn_plan_run_fold(cbn_plan* plan, int64_t n_queries, const float* const* evi
     if (!plan) return set_err(CBN_E_ARG, "null plan");
     if (!fold_rows || fold_n_elems <= 0) return cbn_plan_run(plan, n_queries, evidence, n_evidence, max_bits, out,
                                                              flags | CBN_RUN_RAW, stream);
-    if (!plan->fast || !plan->staged || plan->direct || plan->param)
+    if (plan->sel.kernel != TableKernel::Staged || plan->direct || plan->param)
         return set_err(CBN_E_UNSUPPORTED, "cbn_plan_run_fold: needs a staged (paired N = 32) table plan");
     if (fold_n_elems % 4 || reinterpret_cast<uintptr_t>(fold_rows) % 16 || !fold_words || fold_n_words < 1 ||
         fold_n_words > kFoldW * kWave)
@@ -4143,22 +3712,18 @@ int cbn_plan_check(cbn_plan* plan) {
     return CBN_OK;
 }
 
-int64_t cbn_plan_fused_capacity(const cbn_plan* plan) { return plan ? fused_capacity(plan) : 0; }
+int64_t cbn_plan_fused_capacity(const cbn_plan* plan) { return plan ? plan_fused_capacity(plan) : 0; }
 
 int32_t cbn_plan_flags(const cbn_plan* plan) {
     if (!plan) return 0;
-    return (plan->fast ? CBN_PLAN_FAST : 0) | (plan->use_lds ? CBN_PLAN_LDS : 0) |
-           (plan->paired ? CBN_PLAN_PAIRED : 0) | (plan->staged ? CBN_PLAN_STAGED : 0) |
-           (plan->fused_ok ? CBN_PLAN_FUSED : 0) | (plan->param ? CBN_PLAN_PARAMETRIC : 0) |
-           (plan->vpl == 2 ? CBN_PLAN_VPL2 : 0) | (plan->direct ? CBN_PLAN_DIRECT : 0) |
-           (plan->cols ? CBN_PLAN_COLS : 0) | (plan->slots ? CBN_PLAN_SLOTS : 0) |
-           (reduce_native(plan) ? CBN_PLAN_ARGMAX | CBN_PLAN_MOMENTS | CBN_PLAN_QUANTILE : 0);
+    return table_flags(plan->sel) | (plan->fused_ok ? CBN_PLAN_FUSED : 0) | (plan->param ? CBN_PLAN_PARAMETRIC : 0) |
+           (plan->direct ? CBN_PLAN_DIRECT : 0);
 }
 
 int32_t cbn_plan_max_words(const cbn_plan* plan) {
     if (plan && plan->param) return param_max_words(plan->param);
     if (plan && plan->direct) return direct_max_words(plan->direct);
-    return plan && plan->fast ? plan->max_slots : 0;
+    return plan && plan->sel.fast() ? plan->sel.max_slots : 0;
 }
 
 int cbn_scale(float* out, int64_t n, const uint32_t* max_bits, int32_t n_max, void* stream) {

@@ -19,7 +19,7 @@
 extern "C" {
 #endif
 
-#define CBN_AMD_ABI_VERSION 5
+#define CBN_AMD_ABI_VERSION 6
 
 #define CBN_MAX_PARENTS 8    /* parents per node handled by one factor descriptor */
 #define CBN_MAX_EVIDENCE 256 /* distinct evidence columns per query batch        */
@@ -436,6 +436,38 @@ typedef struct cbn_param_info {
     int32_t generic, nc, n_chunks, hmax, mode, tab, m1, parts, block_threads, max_blocks, lds_bytes, lds_limit;
 } cbn_param_info;
 int cbn_plan_param_info(const cbn_plan* plan, cbn_param_info* out);
+
+/* What cbn_plan_create would decide for these descriptors on a device of n_cu
+ * compute units, under the process's diagnostic switches -- without touching
+ * a device: the descriptors' integers are read and their pointers only tested
+ * for NULL, so this runs on a machine without a GPU.  Same validation, error
+ * codes and messages as cbn_plan_create.  Set struct_bytes to
+ * sizeof(struct cbn_table_plan_info) before the call (CBN_E_ARG otherwise).
+ *   flags         cbn_plan_flags of the plan without CBN_PLAN_FUSED
+ *   kernel        a CBN_TABLE_KERNEL_* value
+ *   vpl, lanes    float4 chunks of a query row per lane, lanes per query (0 on generic plans)
+ *   row_stride    floats between table rows (>= n_samples)
+ *   prefix        leading 1-row factors folded into the next (k_query_staged)
+ *   lds_tab_floats  floats of small tables a global-table plan copies to LDS
+ *   lds_bytes, blocks_per_cu   the kernel's dynamic LDS request and the grid's blocks per CU
+ *   max_slots     cbn_plan_max_words
+ *   fused_candidate  1: the single launch is used if the occupancy query at plan creation passes
+ *   table_bytes   cbn_plan_table_bytes
+ *   fused_capacity   cbn_plan_fused_capacity if that query passes (0: never fused)
+ * Added in ABI 6 (additive).  No reference counterpart. */
+#define CBN_TABLE_KERNEL_GENERIC 0     /* k_query */
+#define CBN_TABLE_KERNEL_FAST 1        /* k_query_fast */
+#define CBN_TABLE_KERNEL_PAIRED_FAST 2 /* k_query_fast on the N = 32 bank-half layout */
+#define CBN_TABLE_KERNEL_STAGED 3      /* k_query_staged */
+#define CBN_TABLE_KERNEL_COLS 4        /* k_query_cols */
+#define CBN_TABLE_KERNEL_SLOTS 5       /* k_query_slots */
+struct cbn_table_plan_info {
+    int32_t struct_bytes, flags, kernel, vpl, lanes, row_stride, prefix, lds_tab_floats, lds_bytes, blocks_per_cu,
+        max_slots, fused_candidate;
+    int64_t table_bytes, fused_capacity;
+};
+int cbn_table_plan_info(const cbn_factor_desc* factors, int32_t n_factors, int32_t n_samples, int32_t n_cu,
+                        struct cbn_table_plan_info* out);
 
 /* Test hook: mark the plan as if a single-launch call had timed out in its
  * grid barrier, so the next cbn_plan_run returns CBN_E_TIMEOUT (exercises the

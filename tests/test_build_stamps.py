@@ -39,7 +39,8 @@ def _fake_tree(tmp_path, monkeypatch):
         shutil.copy(p, dst)
     st.ROOT, st.PKG, st.CSRC = str(tmp_path), str(pkg), str(pkg / "csrc")
     st.LIB_SOURCES = [str(pkg / "csrc" / os.path.basename(p)) for p in st.LIB_SOURCES]
-    st.LIB_HEADERS = [str(pkg / "csrc" / "cbn_internal.h"), str(tmp_path / "include" / "cbn_amd.h")]
+    st.LIB_HEADERS = [str(pkg / "csrc" / "cbn_internal.h"), str(pkg / "csrc" / "cbn_table_plan.h"),
+                      str(tmp_path / "include" / "cbn_amd.h")]
     st.HOST_SOURCES = [str(pkg / "csrc" / "host_fast.cpp")]
     calls = []
 

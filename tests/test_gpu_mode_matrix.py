@@ -4,9 +4,10 @@ The four fast-path query kernels (``k_query_staged``, ``k_query_fast``,
 ``k_query_cols``, ``k_query_slots``) are each compiled in five modes (max,
 write, fused, raw, arg-max) and share one set of mode epilogues
 (csrc/cbn_infer.hip: ``batch_max``, ``round_epilogue``, ``publish_block_max``,
-``fused_block_max``).  Which kernel a plan reaches is decided in
-``cbn_plan_create``; every family below asserts its ``cbn_plan_flags`` so a
-plan cannot silently land elsewhere:
+``fused_block_max``).  Which kernel a plan reaches is decided by the planner
+(csrc/cbn_table_plan.h; DESIGN.md, "Table plans: one host planner, one
+selection"); every family below asserts its ``cbn_plan_flags`` so a plan
+cannot silently land elsewhere:
 
 staged        5-node N = 32 chain, all evidence
 paired        25-node N = 32 chain, all evidence: one past the staged kernel's

@@ -30,7 +30,7 @@ def test_c_abi_rejects_null_arguments():
 
 def test_flag_value_and_abi_version():
     assert _native.CBN_PLAN_MOMENTS == 2048
-    assert _native.load().cbn_abi_version() == 5 == _native.ABI_VERSION
+    assert _native.load().cbn_abi_version() == 6 == _native.ABI_VERSION
     header = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "cbn_amd.h")).read()
     assert "#define CBN_PLAN_MOMENTS 2048" in header
 

@@ -28,7 +28,7 @@ def test_library_exports_every_declared_symbol():
 
 def test_abi_version_and_struct_layout():
     lib = _native.load()
-    assert lib.cbn_abi_version() == 5 == _native.ABI_VERSION
+    assert lib.cbn_abi_version() == 6 == _native.ABI_VERSION
     # cbn_factor_desc: 3 int32 + 2*8 int32 + 3 pointers + 8 pointers (with alignment padding)
     assert ctypes.sizeof(_native.FactorDesc) == 4 * 19 + 4 + 8 * 11
     # cbn_param_model: 8 int32 (family, n_layers, width[5], act) + pointer + 2 float + widths pointer
@@ -45,6 +45,42 @@ def test_abi_version_and_struct_layout():
     body = re.search(r"typedef struct cbn_param_info \{(.*?)\} cbn_param_info;", src, flags=re.S).group(1)
     assert [w.strip() for w in body.replace("int32_t", "").replace(";", "").split(",")] == \
         [n for n, _ in _native.ParamInfo._fields_]
+    # struct cbn_table_plan_info: 12 int32 then 2 int64, in the header's order
+    assert ctypes.sizeof(_native.TablePlanInfo) == 4 * 12 + 8 * 2
+    body = re.search(r"struct cbn_table_plan_info \{(.*?)\};", src, flags=re.S).group(1)
+    names = [w.strip() for w in re.sub(r"int(32|64)_t", "", body).replace(";", ",").split(",") if w.strip()]
+    assert names == [n for n, _ in _native.TablePlanInfo._fields_]
+
+
+def test_table_plan_info_argument_errors_are_reported_without_gpu():
+    """cbn_table_plan_info refuses null arguments, a struct of another size and
+    bad descriptors (cbn_plan_create's messages) without touching a device."""
+    lib = _native.load()
+    info = _native.TablePlanInfo()
+    f = (_native.FactorDesc * 1)()
+    assert lib.cbn_table_plan_info(None, 0, 4, 256, ctypes.byref(info)) == _native.CBN_E_ARG
+    assert b"bad arguments" in lib.cbn_last_error()
+    assert lib.cbn_table_plan_info(f, 1, 4, 256, None) == _native.CBN_E_ARG
+    assert lib.cbn_table_plan_info(f, 1, 4, 256, ctypes.byref(info)) == _native.CBN_E_ARG
+    assert b"struct_bytes" in lib.cbn_last_error()
+    info.struct_bytes = ctypes.sizeof(info)
+    f[0].kind = 7
+    assert lib.cbn_table_plan_info(f, 1, 4, 256, ctypes.byref(info)) == _native.CBN_E_ARG
+    assert b"factor 0: bad kind 7" in lib.cbn_last_error()
+    f[0].kind, f[0].n_parents = 2, 9
+    assert lib.cbn_table_plan_info(f, 1, 4, 256, ctypes.byref(info)) == _native.CBN_E_LIMIT
+    assert lib.cbn_table_plan_info(f, 1, 8192, 256, ctypes.byref(info)) == _native.CBN_E_LIMIT
+    assert b"N_max 8192 too large" in lib.cbn_last_error()
+    f[0].kind, f[0].n_parents = 0, 0
+    assert lib.cbn_table_plan_info(f, 1, 4, 256, ctypes.byref(info)) == _native.CBN_E_ARG
+    assert b"missing cpd/node samples" in lib.cbn_last_error()
+    f[0].cpd, f[0].node_sample_idx, f[0].node_card = 16, 16, 4
+    assert lib.cbn_table_plan_info(f, 1, 4, 256, ctypes.byref(info)) == 0
+    # one root at N = 4: one lane per query, the table in LDS -> k_query_cols, two fused rounds of 256 x 1024 queries
+    assert _native.TABLE_KERNELS[info.kernel] == "cols" and info.lanes == 1 and info.vpl == 1
+    assert info.flags == (_native.CBN_PLAN_FAST | _native.CBN_PLAN_LDS | _native.CBN_PLAN_COLS | _native.CBN_PLAN_ARGMAX |
+                          _native.CBN_PLAN_MOMENTS | _native.CBN_PLAN_QUANTILE)
+    assert info.fused_candidate == 1 and info.fused_capacity == 2 * 256 * 1024 and info.max_slots == 512
 
 
 def test_param_info_argument_errors_are_reported_without_gpu():

@@ -41,7 +41,7 @@ def test_c_abi_rejects_null_and_bad_arguments():
 
 def test_flag_values_and_abi_version():
     assert _native.CBN_PLAN_QUANTILE == 4096 and _native.CBN_MAX_QUANTILES == 16
-    assert _native.load().cbn_abi_version() == 5 == _native.ABI_VERSION
+    assert _native.load().cbn_abi_version() == 6 == _native.ABI_VERSION
     header = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "cbn_amd.h")).read()
     assert "#define CBN_PLAN_QUANTILE 4096" in header and "#define CBN_MAX_QUANTILES 16" in header
 
