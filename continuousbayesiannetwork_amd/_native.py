@@ -50,6 +50,13 @@ CBN_FAMILY_LOGISTIC = 2
 CBN_ACT = {"tanh": 1, "relu": 2, "sigmoid": 3, "leakyrelu": 4, "gelu": 5, "elu": 6}
 CBN_INPUT_FREE = -1
 CBN_INPUT_ONE = -2
+CBN_INPUT_WIDE_BASE = -16
+
+
+def CBN_INPUT_WIDE(slot: int) -> int:
+    """``CBN_INPUT_WIDE(slot)`` of include/cbn_amd.h: evidence column ``slot``
+    read as a [Q, N] column of per-query parent values."""
+    return CBN_INPUT_WIDE_BASE - int(slot)
 
 _c_float_p = ctypes.POINTER(ctypes.c_float)
 _c_int_p = ctypes.POINTER(ctypes.c_int32)
@@ -177,6 +184,7 @@ _SIGNATURES = {
     "cbn_plan_check": (ctypes.c_int, [ctypes.c_void_p]),
     "cbn_plan_flags": (ctypes.c_int32, [ctypes.c_void_p]),
     "cbn_plan_param_info": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ParamInfo)]),
+    "cbn_plan_param_split": (ctypes.c_int, [ctypes.c_void_p, _c_int_p, _c_int_p]),
     "cbn_table_plan_info": (ctypes.c_int, [ctypes.POINTER(FactorDesc), ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                            ctypes.POINTER(TablePlanInfo)]),
     "cbn_scale": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p]),
@@ -310,6 +318,15 @@ def param_info(handle) -> dict:
     info = ParamInfo()
     check(load().cbn_plan_param_info(handle, ctypes.byref(info)), "cbn_plan_param_info")
     return {n: int(getattr(info, n)) for n, _ in ParamInfo._fields_}
+
+
+def param_split(handle) -> list:
+    """``cbn_plan_param_split`` of a parametric plan's handle: the factor
+    ranges' boundaries [b0, .., b_parts] of the split its next call launches."""
+    parts = ctypes.c_int32()
+    bounds = (ctypes.c_int32 * 8)()
+    check(load().cbn_plan_param_split(handle, ctypes.byref(parts), bounds), "cbn_plan_param_split")
+    return [int(bounds[p]) for p in range(parts.value + 1)]
 
 
 def table_plan_info(descs, n_factors: int, n_samples: int, n_cu: int) -> dict:

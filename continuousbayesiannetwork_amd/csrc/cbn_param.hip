@@ -39,6 +39,10 @@ constexpr int kQThreads = 512;  // query kernel: 8 waves per block, so the <= 10
 constexpr int kColPad = 32;
 constexpr int kInputNone = -3;  // unused model input slot (reads the {0, 1} cell)  // sample / constant rows padded to the widest column chunk
 
+// CBN_INPUT_WIDE(slot) <= -16: evidence column `slot` read as [Q, N]
+__host__ __device__ __forceinline__ bool slot_is_wide(int sl) { return sl <= CBN_INPUT_WIDE(0); }
+__host__ __device__ __forceinline__ int wide_slot(int sl) { return CBN_INPUT_WIDE(0) - sl; }
+
 #define PHIP_TRY(expr)                                                                    \
     do {                                                                                  \
         hipError_t _e = (expr);                                                           \
@@ -70,7 +74,8 @@ struct alignas(16) PRec {
     float inv_scale;  // fp32 1 / scale (Newton-refined division by the scale)
     int free_mask;    // bit i: model input i is a free parent (sampled per combo)
     int pw_off;       // one-hidden-layer models: image offset of the pair-packed weights (0: none)
-    int pad[4];
+    int wide_mask;    // bit i: model input i is a wide evidence input (CBN_INPUT_WIDE: N values per query)
+    int pad[3];
 };
 static_assert(sizeof(PRec) == 128, "PRec layout");
 constexpr int kRecFloats = sizeof(PRec) / 4;
@@ -894,7 +899,10 @@ struct FSplit {
 // e.g. full evidence): the free-combo mean and its TwoSum state (2 x NC
 // registers) are not compiled, which keeps the wave within the register
 // budget of the occupancy above.
-template <int NC, int HMAX, int MODE, bool TAB, bool M1>
+// WIDE: the forms launched by plans with a wide evidence input
+// (CBN_INPUT_WIDE); every other plan launches the WIDE = false forms, which
+// compile none of the wide decode.
+template <int NC, int HMAX, int MODE, bool TAB, bool M1, bool WIDE = false>
 __global__ void __launch_bounds__(kQThreads)
 __attribute__((amdgpu_waves_per_eu(!M1 ? 1 : HMAX == 0 ? CBN_WPE_LIN : HMAX == 1 ? (NC <= 16 ? CBN_WPE_MLP : 4) : 1, 8)))
 k_param_query(const float* __restrict__ img, int cst_off, int nf, PEv ev, long long Q, int N, int L, int QW,
@@ -910,8 +918,16 @@ k_param_query(const float* __restrict__ img, int cst_off, int nf, PEv ev, long l
         for (int e = threadIdx.x; e < nf * kMaxP; e += blockDim.x) {
             const int sl = rec[e / kMaxP].in_slot[e % kMaxP];
             InCol c;
-            c.p = sl >= 0 ? ev.p[sl] : (sl == CBN_INPUT_ONE ? cst + 1 : cst);
-            c.stride = sl >= 0 ? 1 : 0;
+            if constexpr (WIDE) {
+                // (a wide input's entry is its column base: element q, in bounds, is what the
+                // pre-loop load reads; every combo overwrites it with element q N + a)
+                const int es = slot_is_wide(sl) ? wide_slot(sl) : sl;
+                c.p = es >= 0 ? ev.p[es] : (sl == CBN_INPUT_ONE ? cst + 1 : cst);
+                c.stride = es >= 0 ? 1 : 0;
+            } else {
+                c.p = sl >= 0 ? ev.p[sl] : (sl == CBN_INPUT_ONE ? cst + 1 : cst);
+                c.stride = sl >= 0 ? 1 : 0;
+            }
             incol[e] = c;
         }
         __syncthreads();
@@ -941,6 +957,34 @@ k_param_query(const float* __restrict__ img, int cst_off, int nf, PEv ev, long l
 #pragma unroll
         for (int j = 0; j < NC; ++j) acc[j] = 1.f;  // out_pdf = ones (bayesian_network.py:269)
         float z[kMaxP];
+        // WIDE forms: model inputs of combo c of factor f (M > 1).  The combo
+        // index walks the free and the wide inputs in meshgrid 'ij' order, the
+        // last one fastest (node.py:335-375).  A free input reads its sample
+        // row in the image (wave-uniform); a wide input reads this lane's own
+        // value col[qs N + a] of the [Q, N] evidence column (64-bit element
+        // index: Q N can pass 2^30; the clamped qs keeps tail lanes in
+        // bounds).  wide_mask is wave-uniform; a factor without wide inputs
+        // takes the free branch of every input.
+        [[maybe_unused]] auto combo_wide = [&](int fm, int wm, int f, const float* __restrict__ FS, int c,
+                                               float (&zz)[kMaxP]) {
+            const long long qn = qs * (long long)N;
+            int cc = c;
+#pragma unroll
+            for (int i = kNMax - 1; i >= 0; --i) {
+                if ((fm | wm) & (1 << i)) {
+                    const int qd = cc / N;
+                    const int a = cc - qd * N;
+                    if (wm & (1 << i)) {
+                        const float* col = TAB ? reinterpret_cast<const PEv4*>(ev.p)[f].p[i < kTabIn ? i : 0]
+                                               : incol[f * kMaxP + i].p;
+                        zz[i] = gload(col, qn + a);
+                    } else {
+                        zz[i] = FS[i * N + a];
+                    }
+                    cc = qd;
+                }
+            }
+        };
         const int fa = active ? f0 : f1;  // an idle wave (batch tail) skips its factors
         if constexpr (!(M1 && TAB)) {  // (the M1 table loop loads its own, two factors ahead)
             if (TAB) load_inputs_tab(ev, fa < nf ? fa : nf - 1, qb, z);
@@ -1024,6 +1068,9 @@ k_param_query(const float* __restrict__ img, int cst_off, int nf, PEv ev, long l
                     const float* FS = img + r.fs_off;
                     const int fm = r.free_mask;
                     for (int c = 0; c < r.M; ++c) {
+                        if constexpr (WIDE) {
+                            combo_wide(fm, r.wide_mask, f, FS, c, z);
+                        } else {
                         int cc = c;  // meshgrid 'ij' order: last free input fastest (node.py:335-375)
 #pragma unroll
                         for (int i = kMaxP - 1; i >= 0; --i) {
@@ -1032,6 +1079,7 @@ k_param_query(const float* __restrict__ img, int cst_off, int nf, PEv ev, long l
                                 z[i] = FS[i * N + (cc - qd * N)];
                                 cc = qd;
                             }
+                        }
                         }
                         add_row<NC, MODE>(mode, fx, cx, S, sc, isc, nm, query_mu<HMAX, kNMax>(r, img, W, z, deep));
                     }
@@ -1152,6 +1200,9 @@ k_param_query(const float* __restrict__ img, int cst_off, int nf, PEv ev, long l
                                         const float* FS = img + r.fs_off;
                                         const int fm = r.free_mask;
                                         for (int c = 0; c < r.M; ++c) {
+                                            if constexpr (WIDE) {
+                                                combo_wide(fm, r.wide_mask, f, FS, c, zt);
+                                            } else {
                                             int cc = c;
 #pragma unroll
                                             for (int i = kMaxP - 1; i >= 0; --i) {
@@ -1160,6 +1211,7 @@ k_param_query(const float* __restrict__ img, int cst_off, int nf, PEv ev, long l
                                                     zt[i] = FS[i * N + (cc - qd * N)];
                                                     cc = qd;
                                                 }
+                                            }
                                             }
                                             add_row<NC, MODE>(mode, fx, cx, S, sc, isc, nm, query_mu<HMAX, kNMax>(r, img, W, zt, deep));
                                         }
@@ -1338,6 +1390,9 @@ __device__ float mlp_gen(const float* __restrict__ W, const int* __restrict__ wi
 
 // model inputs of combo c into A: evidence of query q, free-parent sample
 // points (meshgrid 'ij' order: the last free input fastest), constant 1
+// WIDE (the query kernel): a slot value CBN_INPUT_WIDE(s) is one more axis of
+// the combo index, read per query from the [Q, N] evidence column s
+template <bool WIDE>
 __device__ __forceinline__ void gen_inputs(const float* __restrict__ img, const GRec& r, const PEv* ev, long long q,
                                            int c, int N, float* A, int T) {
     const int* slots = reinterpret_cast<const int*>(img + r.slots_off);
@@ -1352,11 +1407,16 @@ __device__ __forceinline__ void gen_inputs(const float* __restrict__ img, const 
             const int qd = cc / N;
             v = FS[i * N + (cc - qd * N)];
             cc = qd;
+        } else if (WIDE && slot_is_wide(sl)) {
+            const int qd = cc / N;
+            v = gload(ev->p[wide_slot(sl)], q * (long long)N + (cc - qd * N));
+            cc = qd;
         }
         A[i * T] = v;
     }
 }
 
+template <bool WIDE>
 __global__ void __launch_bounds__(256) k_param_query_gen(const float* __restrict__ img, int nf, PEv ev, long long Q,
                                                          int N, int L, int wbuf, int n_words,
                                                          unsigned* __restrict__ max_out, float* __restrict__ out) {
@@ -1388,7 +1448,7 @@ __global__ void __launch_bounds__(256) k_param_query_gen(const float* __restrict
             const int* widths = reinterpret_cast<const int*>(img + r.widths_off);
             const int mode = mode_of(r.family, r.unit != 0);
             if (r.M == 1) {
-                gen_inputs(img, r, &ev, q, 0, N, A, T);
+                gen_inputs<WIDE>(img, r, &ev, q, 0, N, A, T);
                 const float mu = mlp_gen(W, widths, r.n_layers, r.act, A, B, T);
 #pragma unroll
                 for (int j = 0; j < kGenNC; ++j) acc[j] = acc[j] * pdf_eval(mode, r.scale, r.inv_scale, r.norm, S[j], mu);
@@ -1398,7 +1458,7 @@ __global__ void __launch_bounds__(256) k_param_query_gen(const float* __restrict
 #pragma unroll
             for (int j = 0; j < kGenNC; ++j) fx[j] = cx[j] = 0.f;
             for (int c = 0; c < r.M; ++c) {
-                gen_inputs(img, r, &ev, q, c, N, A, T);
+                gen_inputs<WIDE>(img, r, &ev, q, c, N, A, T);
                 const float mu = mlp_gen(W, widths, r.n_layers, r.act, A, B, T);
 #pragma unroll
                 for (int j = 0; j < kGenNC; ++j) two_sum(fx[j], cx[j], pdf_eval(mode, r.scale, r.inv_scale, r.norm, S[j], mu));
@@ -1445,7 +1505,7 @@ __global__ void __launch_bounds__(256) k_param_const_gen(float* __restrict__ img
         const int js = j < N ? j : N - 1;
         float s = 0.f, sc = 0.f;
         for (int c = 0; c < r.M; ++c) {
-            gen_inputs(img, r, nullptr, 0, c, N, A, T);
+            gen_inputs<false>(img, r, nullptr, 0, c, N, A, T);
             two_sum(s, sc, pdf_eval(mode, r.scale, r.inv_scale, r.norm, S[js],
                                     mlp_gen(img + r.w_off, widths, r.n_layers, r.act, A, B, T)));
         }
@@ -1641,6 +1701,7 @@ struct ParamPlan {
     float* d_image = nullptr;
     int* d_which = nullptr;
     int image_floats = 0;
+    bool any_wide = false; // some factor has a wide evidence input: the WIDE kernel forms
     bool generic = false;  // GRec image, k_param_query_gen (models beyond the fast kernels)
     int wbuf = 0;          // generic: floats per LDS activation buffer
     int gT = 0;            // generic: threads per block
@@ -1661,10 +1722,13 @@ size_t query_lds(const cbn::ParamPlan* pp, int nc, bool tab, int parts, int* com
     return lds;
 }
 
-template <int NC, int HMAX, int MODE, bool M1 = false, bool TAB = (MODE < 4)>
+template <int NC, int HMAX, int MODE, bool M1 = false, bool TAB = (MODE < 4), bool WIDE = false>
 void launch_query_t(const cbn::ParamPlan* pp, unsigned grid, const PEv& ev, long long Q, int QW, int L,
                     unsigned* words, float* out, hipStream_t s, int parts) {
-    allow_deep(&k_param_query<NC, HMAX, MODE, TAB, M1>);
+    if constexpr (!M1 && !WIDE) {
+        if (pp->any_wide) return launch_query_t<NC, HMAX, MODE, M1, TAB, true>(pp, grid, ev, Q, QW, L, words, out, s, parts);
+    }
+    allow_deep(&k_param_query<NC, HMAX, MODE, TAB, M1, WIDE>);
     FSplit sp;
     memset(&sp, 0, sizeof(sp));
     sp.parts = parts;
@@ -1678,7 +1742,7 @@ void launch_query_t(const cbn::ParamPlan* pp, unsigned grid, const PEv& ev, long
     sp.screen = guard ? pp->guard_screen[parts] : 0.f;
     sp.mono = pp->mono && guard ? 1 : 0;
     const size_t lds = query_lds(pp, NC, TAB, parts, &sp.comb_off);
-    hipLaunchKernelGGL((k_param_query<NC, HMAX, MODE, TAB, M1>), dim3(grid), dim3(query_block_threads(parts)), lds, s,
+    hipLaunchKernelGGL((k_param_query<NC, HMAX, MODE, TAB, M1, WIDE>), dim3(grid), dim3(query_block_threads(parts)), lds, s,
                        pp->d_image,
                        pp->cst_off, pp->nf, ev, Q, pp->N, L, QW, pp->max_slots, words, out, sp);
 }
@@ -1789,7 +1853,8 @@ int cbn::param_run(cbn_plan* plan, int64_t n_queries, const float* const* eviden
     if (specialised(pp->hmax, pp->mode)) {  // table mode: one pointer per (factor, input)
         for (size_t e = 0; e < pp->in_slot.size(); ++e) {
             const int sl = pp->in_slot[e];
-            ev.p[e] = sl >= 0 ? evidence[sl] : nullptr;  // not evidence: not loaded (z = 0 / a free combo's sample)
+            // not evidence: not loaded (z = 0 / a free combo's sample); a wide input: its column base
+            ev.p[e] = sl >= 0 ? evidence[sl] : slot_is_wide(sl) ? evidence[wide_slot(sl)] : nullptr;
         }
     } else {
         for (int i = 0; i < n_evidence; ++i) ev.p[i] = evidence[i];
@@ -1801,11 +1866,17 @@ int cbn::param_run(cbn_plan* plan, int64_t n_queries, const float* const* eviden
         const long long tasks = n_queries * L;
         long long grid = std::max(1LL, std::min((tasks + pp->gT - 1) / pp->gT, (long long)pp->max_slots));
         const size_t lds = sel.lds;
-        allow_deep(&k_param_query_gen);
         const bool raw = (flags & CBN_RUN_RAW) != 0;
         unsigned* words = raw ? max_bits : plan->d_sync + kMaxWordOff;
-        hipLaunchKernelGGL(k_param_query_gen, dim3((unsigned)grid), dim3(pp->gT), lds, s, pp->d_image, pp->nf, ev,
-                           (long long)n_queries, pp->N, L, pp->wbuf, pp->max_slots, words, out);
+        if (pp->any_wide) {
+            allow_deep(&k_param_query_gen<true>);
+            hipLaunchKernelGGL(k_param_query_gen<true>, dim3((unsigned)grid), dim3(pp->gT), lds, s, pp->d_image, pp->nf,
+                               ev, (long long)n_queries, pp->N, L, pp->wbuf, pp->max_slots, words, out);
+        } else {
+            allow_deep(&k_param_query_gen<false>);
+            hipLaunchKernelGGL(k_param_query_gen<false>, dim3((unsigned)grid), dim3(pp->gT), lds, s, pp->d_image, pp->nf,
+                               ev, (long long)n_queries, pp->N, L, pp->wbuf, pp->max_slots, words, out);
+        }
         PHIP_TRY(hipGetLastError());
         if (raw) return CBN_OK;
         if (reinterpret_cast<uintptr_t>(out) % 16) return set_err(CBN_E_ARG, "cbn_plan_run: out must be 16-B aligned");
@@ -1852,6 +1923,7 @@ int create_param_generic(const cbn_param_factor* factors, int n_factors, int N, 
     long long off = (long long)n_factors * (sizeof(GRec) / 4);
     const long long row = (N + kColPad - 1) / kColPad * kColPad;
     int ns = 0, wbuf = 1;
+    bool any_wide = false;
     for (int f = 0; f < n_factors; ++f) {
         const cbn_param_factor& h = factors[f];
         GRec& r = recs[f];
@@ -1872,6 +1944,16 @@ int create_param_generic(const cbn_param_factor* factors, int n_factors, int N, 
                 if (sl >= CBN_MAX_EVIDENCE) return set_err(CBN_E_LIMIT, "factor %d: evidence slot %d", f, sl);
                 ns = std::max(ns, sl + 1);
                 ++n_obs;
+            } else if (slot_is_wide(sl)) {  // observed, and an axis of the combo mean
+                const int ws = wide_slot(sl);
+                if (ws >= CBN_MAX_EVIDENCE) return set_err(CBN_E_LIMIT, "factor %d: evidence slot %d", f, ws);
+                if (h.kind != CBN_FACTOR_QUERY)
+                    return set_err(CBN_E_ARG, "factor %d: a wide evidence input needs a QUERY factor", f);
+                ns = std::max(ns, ws + 1);
+                ++n_obs;
+                any_wide = true;
+                M *= N;
+                if (M >= (1LL << 31)) return set_err(CBN_E_LIMIT, "factor %d: too many free-parent combos", f);
             } else if (sl == CBN_INPUT_FREE) {
                 ++n_free;
                 M *= N;
@@ -1928,6 +2010,7 @@ int create_param_generic(const cbn_param_factor* factors, int n_factors, int N, 
     }
     ParamPlan* pp = new ParamPlan();
     pp->generic = true;
+    pp->any_wide = any_wide;
     pp->nf = n_factors;
     pp->N = N;
     pp->ns = ns;
@@ -2057,6 +2140,16 @@ int cbn_plan_create_param(const cbn_param_factor* factors, int32_t n_factors, in
                 if (sl >= CBN_MAX_EVIDENCE) return set_err(CBN_E_LIMIT, "factor %d: evidence slot %d", f, sl);
                 ns = std::max(ns, sl + 1);
                 ++n_obs;
+            } else if (slot_is_wide(sl)) {  // observed, and an axis of the combo mean
+                const int ws = wide_slot(sl);
+                if (ws >= CBN_MAX_EVIDENCE) return set_err(CBN_E_LIMIT, "factor %d: evidence slot %d", f, ws);
+                if (h.kind != CBN_FACTOR_QUERY)
+                    return set_err(CBN_E_ARG, "factor %d: a wide evidence input needs a QUERY factor", f);
+                ns = std::max(ns, ws + 1);
+                ++n_obs;
+                r.wide_mask |= 1 << i;
+                M *= N;
+                if (M >= (1LL << 31)) return set_err(CBN_E_LIMIT, "factor %d: too many free-parent combos", f);
             } else if (sl == CBN_INPUT_FREE) {
                 ++n_free;
                 r.free_mask |= 1 << i;
@@ -2107,6 +2200,7 @@ int cbn_plan_create_param(const cbn_param_factor* factors, int32_t n_factors, in
     pp->N = N;
     pp->ns = ns;
     pp->hmax = hmax;
+    for (const PRec& r : recs) pp->any_wide = pp->any_wide || r.wide_mask != 0;
     for (const PRec& r : recs) {
         pp->deep = std::max(pp->deep, deep_bytes(r.m, hmax, kQThreads));
         pp->deep_const = std::max(pp->deep_const, deep_bytes(r.m, hmax));
@@ -2302,6 +2396,21 @@ int cbn_plan_param_info(const cbn_plan* plan, cbn_param_info* out) {
     out->max_blocks = pp->max_slots;
     out->lds_bytes = (int32_t)v.lds;
     out->lds_limit = kDynLdsMax;
+    return CBN_OK;
+}
+
+int cbn_plan_param_split(const cbn_plan* plan, int32_t* parts, int32_t* bounds) {
+    if (!plan || !parts || !bounds) return set_err(CBN_E_ARG, "cbn_plan_param_split: null argument");
+    if (!plan->param) return set_err(CBN_E_ARG, "cbn_plan_param_split: not a parametric plan");
+    const ParamPlan* pp = plan->param;
+    const ParamSel v = param_select(pp);
+    *parts = v.parts;
+    for (int p = 0; p < 8; ++p) bounds[p] = 0;
+    if (v.generic) {
+        bounds[1] = pp->nf;
+    } else {
+        for (int p = 0; p <= v.parts; ++p) bounds[p] = pp->split[v.parts][p];
+    }
     return CBN_OK;
 }
 

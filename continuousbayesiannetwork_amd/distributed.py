@@ -243,6 +243,17 @@ def _sharded_on_plan(eng, plan, fp, target_node, evidence_shard, N_max, group, g
     if n == 0:  # no launch checks an empty shard's columns: raise the reference's shape errors here
         wide = eng.check_columns(plan, evidence_shard)  # ([Q, N] columns: the wide direct plan's raw launch)
     raw = eng.infer_raw(target_node, evidence_shard, N_max, out, fp=fp) if (fp is not None and n > 0) else None
+    per_call = fp is None and eng.rebuilt_param_plan(plan)
+    if per_call and n > 0:
+        # a parametric plan rebuilt per call (redrawn domains) has no fast path; its
+        # [Q, N] columns still run one raw launch, on this call's wide plan
+        raw = eng.raw_wide_call(plan, evidence_shard, out)
+    elif per_call and multi and wide:  # ... and an empty shard of such a call: zero words, the same collectives
+        device = plan.max_bits.device
+        raw = (torch.empty((0, plan.n_samples), dtype=torch.float32, device=device),
+               plan.target_domain.unsqueeze(0).expand(0 if plan.target_observed else 1, -1),
+               torch.zeros(eng.wide_word_count(plan, wide, device), dtype=torch.int32, device=device),
+               lambda r, b: r)
     if raw is None and multi and fp is not None and (fp.words is not None or wide) and n == 0:
         # an empty shard on a raw-capable plan: no rows, zero max words -- the
         # same collectives as the other ranks

@@ -82,8 +82,15 @@ class Plan:
     idx_host: Optional[torch.Tensor] = None  # redrawn plans: host mirror of idx_flat
     redraw: Optional["RedrawProgram"] = None  # redrawn plans: the per-call draws (host_fast.redraw jobs)
     observed: frozenset = frozenset()  # the observed parent columns the plan was built for
+    # a parametric plan rebuilt per call (redrawn domains): the wide plans of
+    # this call ([Q, N] columns -> plan), which carry the same draws and are
+    # destroyed with it
+    wide_children: dict = field(default_factory=dict)
 
     def destroy(self):
+        for wp in self.wide_children.values():
+            wp.destroy()
+        self.wide_children = {}
         if self.handle is not None and self.handle.value:
             _native.load().cbn_plan_destroy(self.handle)
         self.handle = None
@@ -618,11 +625,15 @@ class InferenceEngine:
         plan.reusable = True
         plan.max_bits = torch.zeros(1, dtype=torch.int32, device=device)
 
-    def _materialise_param(self, plan: Plan, device: torch.device):
+    def _materialise_param(self, plan: Plan, device: torch.device, wide=frozenset()):
         """cbn_param_factor per ancestor (include/cbn_amd.h): the estimator's
         packed model, the input wiring (evidence slot / free parent sampled at
         sample_domain / constant 1 for roots) and the sample points -- the
-        values Node.get_prob evaluates (node.py:152-193)."""
+        values Node.get_prob evaluates (node.py:152-193).  ``wide``: observed
+        parents whose evidence column is [Q, N] (_wide_plan): the nodes that
+        expand it (evidence keys != parents, node.py:246-248) read it as
+        CBN_INPUT_WIDE(slot), N per-query values averaged like a free
+        parent's samples."""
         lib = _native.load()
         descs = (_native.ParamFactor * len(plan.factors))()
         keep = []
@@ -643,9 +654,10 @@ class InferenceEngine:
                     if len(spec.parents) != k:
                         raise _native.NativeError(f"node {spec.node}: model has {k} inputs, {len(spec.parents)} parents")
                     samples = torch.zeros((k, N), dtype=torch.float32, device=device)
+                    strict = sorted(spec.observed) == list(spec.parents)
                     for i, p in enumerate(spec.parents):
                         if p in spec.observed:
-                            slots[i] = slot_of[p]
+                            slots[i] = _native.CBN_INPUT_WIDE(slot_of[p]) if (p in wide and not strict) else slot_of[p]
                         else:
                             slots[i] = _native.CBN_INPUT_FREE
                             samples[i] = spec.free_samples[p].to(device=device, dtype=torch.float32)
@@ -796,8 +808,9 @@ class InferenceEngine:
         A width-N column read only through ``.expand`` is accepted by the
         reference as N per-sample values of the observed parent (a per-query
         free parent): those columns are returned (a set, empty when every
-        column is [Q, 1]) and run on a direct plan that averages over them
-        (``_wide_plan``; cbn_direct_factor.parent_ev_width, ABI 5)."""
+        column is [Q, 1]) and run on a wide plan that averages over them
+        (``_wide_plan``: cbn_direct_factor.parent_ev_width for BruteForce
+        networks, CBN_INPUT_WIDE inputs for parametric ones)."""
         N = plan.n_samples
         wide = set()
         for spec in plan.factors:
@@ -1314,22 +1327,38 @@ class InferenceEngine:
         enter the meshgrid like a free parent's samples, node.py:335-375, and
         the factor is their mean).  It shares ``plan``'s sample-index arrays
         (a redrawn plan's draws of this call included; its constant rows are
-        then rebuilt per call).  BruteForce networks only."""
-        if plan.direct is False and any(hasattr(self.bn.nodes_obj[s.node].estimator, "model_desc")
-                                        for s in plan.factors):
-            raise NotImplementedError(
-                "[n_queries, N_max] evidence columns (per-query sample values, node.py:246-248) are evaluated on "
-                "BruteForce networks; the parametric kernels take [n_queries, 1] columns")
-        key = (plan.target, plan.observed, plan.n_samples, frozenset(wide))
-        wp = self._wide_plans.get(key)
-        if wp is not None and wp[0] is plan:
-            return wp[1]
+        then rebuilt per call).
+
+        A parametric plan gets a parametric plan of the same factor specs
+        (``_materialise_param``: CBN_INPUT_WIDE inputs).  Where the base plan
+        is rebuilt per call (redrawn domains) the wide plan holds this call's
+        draws: it is kept on the base plan only (``wide_children``), never in
+        the engine's cache, and destroyed with it after the call's sync."""
         import dataclasses
 
-        wp = dataclasses.replace(plan, handle=None, keep=[], max_bits=None, tables_built=False, direct=False,
-                                 redraw=None, idx_host=None)
-        self._materialise_direct(wp, device, widths={c: plan.n_samples for c in wide}, share_idx=plan)
+        param = plan.direct is False and any(hasattr(self.bn.nodes_obj[s.node].estimator, "model_desc")
+                                             for s in plan.factors)
+        per_call = param and not (plan.deterministic or plan.reusable)
+        key = (plan.target, plan.observed, plan.n_samples, frozenset(wide))
+        if per_call:
+            wp = plan.wide_children.get(key[3])
+        else:
+            wp = self._wide_plans.get(key)
+            wp = wp[1] if (wp is not None and wp[0] is plan) else None
+        if wp is not None:
+            return wp
+        if param:
+            wp = dataclasses.replace(plan, handle=None, keep=[], max_bits=None, tables_built=False, redraw=None,
+                                     idx_host=None, wide_children={})
+            self._materialise_param(wp, device, wide=key[3])
+        else:
+            wp = dataclasses.replace(plan, handle=None, keep=[], max_bits=None, tables_built=False, direct=False,
+                                     redraw=None, idx_host=None, wide_children={})
+            self._materialise_direct(wp, device, widths={c: plan.n_samples for c in wide}, share_idx=plan)
         wp.words = torch.zeros(int(_native.load().cbn_plan_max_words(wp.handle)), dtype=torch.int32, device=device)
+        if per_call:
+            plan.wide_children[key[3]] = wp
+            return wp
         old = self._wide_plans.pop(key, None)
         if old is not None:
             torch.cuda.synchronize()
@@ -1388,6 +1417,46 @@ class InferenceEngine:
             return None
         rows, tdom, words = self._run_wide(fp.plan, evidence, wide, n, fp.device, out, raw=True)
         return rows, tdom, words, self._wide_scale(fp)
+
+    def serving_plan(self, target: str, evidence: Dict[str, torch.Tensor], N_max: int) -> Plan:
+        """The cached plan whose launches serve this call: the wide plan when a
+        column is [Q, N], else the call's own plan (what ``cbn_plan_param_info``
+        / ``cbn_plan_flags`` should be asked about).  Kept plans only: a plan
+        rebuilt per call lives for that call alone."""
+        plan, fp = self.call_plan(target, evidence, N_max)
+        if fp is None:
+            torch.cuda.current_stream(plan.max_bits.device).synchronize()
+            plan.destroy()
+            raise ValueError("serving_plan: this call's plan is rebuilt per call (redrawn sample domains)")
+        wide = self._wide(plan, evidence)
+        return self._wide_plan(plan, wide, fp.device) if wide else plan
+
+    def rebuilt_param_plan(self, plan: Plan) -> bool:
+        """A parametric plan that is rebuilt per call (redrawn sample domains):
+        neither cached nor kept, so it has no fast path."""
+        return (not plan.direct and not plan.deterministic and not plan.reusable
+                and all(hasattr(self.bn.nodes_obj[s.node].estimator, "model_desc") for s in plan.factors))
+
+    def raw_wide_call(self, plan: Plan, evidence, out):
+        """``_raw_wide`` for a parametric plan rebuilt per call (no fast path; the
+        caller destroys the plan, and with it the wide plan, after the call):
+        (rows, target domain, words, scale), or None when no column is [Q, N]
+        or the plan is of another kind."""
+        if not self.rebuilt_param_plan(plan):
+            return None
+        n = next(iter(evidence.values())).shape[0] if len(evidence) else 0
+        wide = self._wide(plan, evidence) if n > 0 else None
+        if not wide:
+            return None
+        device = plan.max_bits.device
+        rows, tdom, words = self._run_wide(plan, evidence, wide, n, device, out, raw=True)
+
+        def scale(rows: torch.Tensor, bits: torch.Tensor):
+            with torch.cuda.device(device):
+                _native.check(_native.load().cbn_scale(_native.ptr(rows), rows.numel(), _native.ptr(bits), bits.numel(),
+                                                       _native.stream_ptr(device)), "cbn_scale")
+            return rows
+        return rows, tdom, words, scale
 
     @staticmethod
     def _wide_scale(fp: "_FastPath"):

@@ -437,6 +437,13 @@ typedef struct cbn_param_info {
 } cbn_param_info;
 int cbn_plan_param_info(const cbn_plan* plan, cbn_param_info* out);
 
+/* The factor split the plan's next call launches: *parts (as
+ * cbn_param_info.parts) and bounds[0 .. parts] (host int32[8]; part p
+ * multiplies the factors bounds[p] .. bounds[p + 1] - 1 in the plan's factor
+ * order; entries past parts are 0).  Read-only; CBN_E_ARG on other plans.
+ * Additive in ABI 6.  No reference counterpart. */
+int cbn_plan_param_split(const cbn_plan* plan, int32_t* parts, int32_t* bounds);
+
 /* What cbn_plan_create would decide for these descriptors on a device of n_cu
  * compute units, under the process's diagnostic switches -- without touching
  * a device: the descriptors' integers are read and their pointers only tested
@@ -513,6 +520,11 @@ int cbn_plan_timing(cbn_plan* plan, int32_t* n_timed, float* avg_max_ms, float* 
 #define CBN_ACT_ELU 6        /* alpha 1 */
 #define CBN_INPUT_FREE -1    /* input = a free parent: its N sample points (mean over combos) */
 #define CBN_INPUT_ONE -2     /* input = constant 1 (root models: neural_network.py:117-119)  */
+/* input = evidence column `slot` read as a contiguous row-major [Q, N] float32
+ * column: N per-query values of an observed parent (node.py:246-248's
+ * .expand(-1, N) of a width-N column), an axis of the combo mean like a free
+ * parent's samples.  Encoded values are <= -16; -3..-15 are errors. */
+#define CBN_INPUT_WIDE(slot) (-16 - (slot))
 
 typedef struct cbn_param_model {
     int32_t family;                     /* CBN_FAMILY_*                                  */
@@ -532,11 +544,19 @@ typedef struct cbn_param_model {
  *                        of pdf(s_j; mu(c))                                  [N]
  *   QUERY              : x[q, j] = mean over the free parents' combos c of
  *                        pdf(s_j; mu(observed values of query q, c))     [Q, N]
- * (node.py:115-204 with bayesian_network.py:271-294's mean over parent axes.) */
+ * (node.py:115-204 with bayesian_network.py:271-294's mean over parent axes.)
+ * A QUERY factor's input may be CBN_INPUT_WIDE(slot): the value of query q at
+ * axis position a is element q * N + a of that evidence column.  Free and wide
+ * inputs are the axes of the combo index c (meshgrid 'ij': the last axis input
+ * fastest), M = N^(free + wide) < 2^31 combos, x = (compensated sum) / M.  A
+ * wide input counts as observed (QUERY iff some parent observed) and is
+ * refused on SCALAR / SHARED factors.  A NaN entry makes that query's row NaN
+ * and touches no other row. */
 typedef struct cbn_param_factor {
     int32_t kind;                         /* CBN_FACTOR_*                            */
     int32_t input_slot[CBN_MAX_PARENTS];  /* per model input: evidence column >= 0,
-                                             CBN_INPUT_FREE or CBN_INPUT_ONE          */
+                                             CBN_INPUT_FREE, CBN_INPUT_ONE or
+                                             CBN_INPUT_WIDE(evidence column)          */
     const float* input_samples;           /* device [width[0]][N]: rows of FREE inputs */
     const float* node_samples;            /* device [N]: the node's evaluation points  */
     cbn_param_model model;

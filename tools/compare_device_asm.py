@@ -5,7 +5,8 @@
 
 A host-side refactor may change the order in which templates are instantiated,
 and with it the order of the functions in the file and the function index the
-compiler puts into local labels (.LBB<fn>_<n>, .Lfunc_end<fn>).  This splits
+compiler puts into local labels (.LBB<fn>_<n>, .Lfunc_end<fn>; the long-branch
+labels .Lpost_getpc<n> are numbered through the whole file).  This splits
 both files at their functions' .globl lines, drops comments, replaces that index,
 and compares each function (code and kernel descriptor, up to
 .end_amdhsa_kernel) and each entry of the metadata note by symbol name.
@@ -27,7 +28,7 @@ def functions(text):
         if name is None or done:
             continue
         line = re.sub(r"\s*;.*$", "", line)
-        line = re.sub(r"\.L(BB|JTI|func_end|func_begin|tmp)\d+", r".L\1N", line)
+        line = re.sub(r"\.L(BB|JTI|func_end|func_begin|tmp|post_getpc)\d+", r".L\1N", line)
         if line.strip():
             lines.append(line)
         done = ".end_amdhsa_kernel" in line
